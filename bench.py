@@ -2,7 +2,7 @@
 """
 bench.py - images/sec of the MI355X conv-net inference hot path (BASELINE.json metric), one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload resnet50_bs256]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload resnet50_bs256] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (child processes, before anything in this
@@ -10,14 +10,23 @@ process touches a GPU) and relays rank 0's JSON line; under torch.distributed.ru
 
 A step = one forward of the workload's batch through `get_model(name)` (fp32 NCHW input resident in HBM -> NHWC 16 bit ->
 fused HIP kernels -> fp32 logits) followed, for N > 1, by the all-gather of the logits. Weak scaling: every rank runs the
-full per-GPU batch. Rank 0 prints ONE JSON line (contract in the task statement) with
+full per-GPU batch. Rank 0 prints ONE JSON line (contract in the task statement): `value` (images/s) and `ms_per_step` of the
+K timed steps.
+
+A plain run does only that: set up, W warm-up steps, K timed steps, the outputs (`--dump-outputs DIR`: the fp32 logits of the
+last timed step, as a caller of the timed path receives them, as DIR/logits.npy; inputs and weights are seeded, so two builds
+compare output for output), the line. `--full` adds the checks and the figures that take runs of their own:
+  checks        every row of the timed batch equals the 8-image eager forward bit for bit (exit 3); for N > 1, the replicas'
+                logits of a common input agree after the weight broadcast (exit 5);
   roofline      the north-star kernel class of the workload (ResNet-50: dense 3x3 vs the 2.5 PFLOP/s dense bf16 MFMA peak;
                 MobileNetV2: stand-alone depthwise vs the 8 TB/s HBM peak; ResNeXt-101: grouped 3x3) timed live with HIP events
                 around every eager launch, beside the committed rocprofv3 all-launch average and PMC traffic, plus `classes`:
                 every kernel class of the forward with us/step, achieved rate and fraction of its roof;
+  latency       one forward of the batch on one stream (graph replay);
   cpu_baseline  the oracle's torch-fp32 CPU forward on the host cores;
-  other_configs (default invocation only) BASELINE configs 3 and 4 - MobileNetV2 bs512, ResNeXt-101 bs256 - timed the same way
-                over 10 steps each, so that they carry a driver-timed number too.
+  other_configs (default workload only) BASELINE configs 3 and 4 - MobileNetV2 bs512, ResNeXt-101 bs256 - timed the same way
+                over 30 steps each, so that they carry a driver-timed number too.
+Without `--full` these keys are null.
 """
 
 import os
@@ -51,6 +60,8 @@ MFMA_PEAK_TFLOPS = 2500.0     # dense bf16/fp16, MI355X_MICROARCH.md "Peak BF16/
 HBM_PEAK_GBS = 8000.0         # HBM3E spec peak, MI355X_MICROARCH.md "HBM3E peak BW"
 TERM_GRACE_S = 10.0                       # launcher: seconds between SIGTERM and SIGKILL for ranks that do not exit
 OTHER_STEPS, OTHER_WARMUP = 30, 5          # timed / warm-up steps of each `other_configs` workload (r4: 10 steps = 17 ms was too short a window)
+DUMP_LIMIT_BYTES = 64 << 20                # --dump-outputs: at most this much in all (a seeded sample of the rows beyond it)
+DUMP_SAMPLE_SEED = 2024
 RIDGE_FLOP_PER_BYTE = MFMA_PEAK_TFLOPS * 1e12 / (HBM_PEAK_GBS * 1e9)     # 312.5: a class above it is MFMA-bound, below it HBM-bound
 
 # Kernel classes. Live timing classifies a launch by what the host asked for; the rocprofv3 / PMC summaries classify a dispatch
@@ -399,9 +410,10 @@ class _StubNet(torch.nn.Module):
         return self.fc(torch.nn.functional.adaptive_avg_pool2d(x, 8).flatten(1))
 
 
-def run_workload(env, workload, args, steps, warmup, profile=False):
+def run_workload(env, workload, args, steps, warmup, profile=False, checks=False):
     """One workload, timed exactly as the contract says: W untimed steps, K timed ones between barrier + synchronize on both sides,
-    MAX over ranks. Returns (result dict, context for the roofline / CPU passes)."""
+    MAX over ranks. `checks` (--full): the replica check after the weight broadcast and the row-by-row check of the timed batch.
+    Returns (result dict, context for the roofline / CPU passes; ctx["y"] is what the last timed step returned)."""
     from pytorchcv_amd.parallel import ShardedInference, broadcast_packed_state, replicas_agree
     from pytorchcv_amd.synth import synth_state_dict, synth_input
     model, batch, klass = WORKLOADS[workload]
@@ -430,7 +442,6 @@ def run_workload(env, workload, args, steps, warmup, profile=False):
     # synthetic N(0,1)-like images: 8 distinct seeded images per rank tiled to the batch (performance is data independent)
     hw = 224 if not env.stub else 32
     base = synth_input(8, 3, hw, hw, seed=rank).to(dev)
-    common = synth_input(8, 3, hw, hw, seed=4242).to(dev)            # the same on every rank: the replica check below
     x = base.repeat((batch + 7) // 8, 1, 1, 1)[:batch].contiguous()
     with torch.no_grad():
         net(x if profile else base)                  # builds and packs every layer (rank 0: the real weights)
@@ -445,11 +456,13 @@ def run_workload(env, workload, args, steps, warmup, profile=False):
         env.sync()
         dist.barrier()
         bcast_s = time.perf_counter() - tb
-        with torch.no_grad():
-            if not replicas_agree(net(common)):      # a tensor the broadcast missed = plausible but different logits on ranks != 0
-                env.fail(5, "replicas disagree on a common input after the weight broadcast")
+        if checks:
+            common = synth_input(8, 3, hw, hw, seed=4242).to(dev)    # the same on every rank
+            with torch.no_grad():
+                if not replicas_agree(net(common)):  # a tensor the broadcast missed = plausible but different logits on ranks != 0
+                    env.fail(5, "replicas disagree on a common input after the weight broadcast")
     y_ref8 = None
-    if not profile:
+    if checks and not profile:
         with torch.no_grad():
             y_ref8 = net(base).clone()               # the 8 distinct images on their own: what every row of the timed batch must equal
     use_graph = args.graph != 0 and not env.stub and not profile
@@ -522,10 +535,11 @@ def run_workload(env, workload, args, steps, warmup, profile=False):
                launchers_timed=getattr(fwd, "tuning", None),
                launcher_choice=("fixed for multi-rank runs (the same on every rank)" if env.use_dist and args.inflight == 0 and args.lanes == 0
                                 else ("timed at capture on this GPU" if args.inflight == 0 and args.lanes == 0 else "flags")),
-               weights_broadcast=(dict(messages=bcast[0], bytes=bcast[1], seconds=round(bcast_s, 4), replicas_agree=True,
-                                       what="packed inference state (RCCL broadcast from rank 0), then every rank's logits of a common "
-                                            "input compared (all-reduce MIN / MAX)") if bcast else None))
-    return res, dict(net=net, x=x, sd_cpu=sd_cpu, model=model, klass=klass, dtype=dtype, batch=batch)
+               weights_broadcast=(dict(messages=bcast[0], bytes=bcast[1], seconds=round(bcast_s, 4), replicas_agree=True if checks else None,
+                                       what="packed inference state (RCCL broadcast from rank 0)" + (
+                                           ", then every rank's logits of a common input compared (all-reduce MIN / MAX)" if checks else
+                                           "; replicas not compared (--full compares them)")) if bcast else None))
+    return res, dict(net=net, x=x, sd_cpu=sd_cpu, model=model, klass=klass, dtype=dtype, batch=batch, y=y)
 
 
 def forward_latency(ctx, samples=24):
@@ -624,6 +638,21 @@ def roofline_of(env, workload, ctx, passes):
                              "fraction of the class's roof (mfma: 2.5 PFLOP/s; hbm: 8 TB/s), committed rocprofv3 all-launch average and PMC "
                              "traffic beside it where collected")
     return roof
+
+
+def dump_outputs(out_dir, y):
+    """--dump-outputs: what the timed path returned in its last step (the fp32 logits, every rank's rows after the all-gather) as
+    out_dir/logits.npy; beyond DUMP_LIMIT_BYTES a fixed, seeded sample of its rows (the same rows on every run of the same shape)."""
+    import numpy as np
+    y = y.detach().float().cpu()
+    if y.numel() * 4 > DUMP_LIMIT_BYTES:
+        n = y.shape[0]
+        g = torch.Generator().manual_seed(DUMP_SAMPLE_SEED)
+        rows = torch.randperm(n, generator=g)[:max(1, DUMP_LIMIT_BYTES // (y[0].numel() * 4))].sort().values
+        y = y[rows]
+        print("bench.py: --dump-outputs: a seeded sample of {} of the {} rows".format(y.shape[0], n), file=sys.stderr)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "logits.npy"), y.contiguous().numpy().astype(np.float32))
 
 
 def visible_gpus():
@@ -745,7 +774,13 @@ def main(argv=None):
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: the workload's batch per GPU (default); strong: --global-batch images split over the ranks (BASELINE config 5: 2048)")
     ap.add_argument("--global-batch", type=int, default=2048)
+    ap.add_argument("--full", action="store_true", help="also the checks (timed rows vs the 8-image forward, replica agreement), "
+                                                        "roofline, latency, cpu_baseline and other_configs; a plain run only times")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the fp32 logits of the last "
+                                                                         "one to DIR/logits.npy (rank 0; all ranks' rows for N > 1)")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     stub = os.environ.get("PCV_BENCH_STUB") == "1"
     # PCV_BENCH_PROFILE=1 (the rocprofv3 / PMC collection runs): nothing but full-batch eager forwards on one lane - no 8-image
     # forwards, no graph, no roofline / CPU passes - so that EVERY dispatch in the profiler's tables is a full-batch launch
@@ -769,8 +804,10 @@ def main(argv=None):
             k, v = kv.split("=")
             _lib.check(_lib.lib().pcv_set_tuning(_lib.ctx_for(env.local_rank), k.encode(), int(v)), _lib.ctx_for(env.local_rank))
 
-    res, ctx = run_workload(env, args.workload, args, args.steps, args.warmup, profile=profile)
-    rank0_extras = env.rank == 0 and not stub and not profile
+    res, ctx = run_workload(env, args.workload, args, args.steps, args.warmup, profile=profile, checks=args.full)
+    if args.dump_outputs and env.rank == 0:
+        dump_outputs(args.dump_outputs, ctx["y"])
+    rank0_extras = env.rank == 0 and not stub and not profile and args.full
     roof = roofline_of(env, args.workload, ctx, max(3, min(args.steps, 10))) if rank0_extras else None
     lat = forward_latency(ctx) if (rank0_extras and args.graph != 0) else None
     cpu = cpu_baseline(ctx["model"], ctx["sd_cpu"]) if (rank0_extras and env.world == 1 and not args.no_cpu_baseline) else None
@@ -780,7 +817,7 @@ def main(argv=None):
         torch.cuda.empty_cache()
         others = {}
         for w in OTHER_CONFIGS:
-            r, c = run_workload(env, w, args, OTHER_STEPS, OTHER_WARMUP)
+            r, c = run_workload(env, w, args, OTHER_STEPS, OTHER_WARMUP, checks=True)
             others[w] = dict(value=r["value"], unit="images/sec", ms_per_step=r["ms_per_step"], steps=OTHER_STEPS, warmup=OTHER_WARMUP, dtype=r["dtype"],
                              launch=r["launch"], rows_checked="every row of the timed batch equals the 8-image eager forward bit for bit",
                              roofline=compact_roofline(roofline_of(env, w, c, 3)), latency=forward_latency(c, samples=20))
@@ -792,7 +829,7 @@ def main(argv=None):
         out = {
             "metric": "images/sec @224x224 ({} bs={}/GPU)".format(model, res["per_gpu_batch"]),
             "value_is": "steady-state throughput: images of the K timed steps / their wall time ({}); the one-forward latency figure of "
-                        "SURVEY 8d is `latency`".format(res["launch"]),
+                        "SURVEY 8d is `latency` (--full)".format(res["launch"]),
             "value": res["value"],
             "unit": "images/sec",
             "n_gpus": env.world,

@@ -24,7 +24,7 @@ def _run(extra_env, *argv, timeout=240):
 
 
 def test_self_launch_world_size_2():
-    p = _run({}, "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "16")
+    p = _run({}, "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "16", "--full")
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, "the parent relays rank 0's ONE JSON line: {}".format(lines)
@@ -81,6 +81,26 @@ def test_single_rank_runs_in_process():
     assert p.returncode == 0, p.stderr[-2000:]
     out = json.loads(p.stdout.strip().splitlines()[-1])
     assert out["n_gpus"] == 1 and out["weights_broadcast"] is None
+
+
+def test_dump_outputs_are_the_last_step_and_repeatable(tmp_path):
+    """--dump-outputs DIR: the fp32 logits of the last timed step (all ranks' rows after the all-gather) as DIR/logits.npy, the
+    same from run to run with the same arguments; a plain run (no --full) compares no replicas."""
+    import numpy as np
+    got = []
+    for i, gpus in enumerate(("1", "1", "2")):
+        d = tmp_path / "d{}".format(i)
+        p = _run({}, "--gpus", gpus, "--steps", "2", "--warmup", "1", "--batch", "8", "--dump-outputs", str(d))
+        assert p.returncode == 0, p.stderr[-2000:]
+        out = json.loads(p.stdout.strip().splitlines()[-1])
+        assert out["steps"] == 2 and out["ms_per_step"] > 0 and out["roofline"] is None and out["latency"] is None
+        if gpus == "2":
+            assert out["weights_broadcast"]["replicas_agree"] is None
+        y = np.load(str(d / "logits.npy"))
+        assert y.dtype == np.float32 and y.shape == (8 * int(gpus), 1000) and np.isfinite(y).all()
+        got.append(y)
+    assert np.array_equal(got[0], got[1])
+    assert np.array_equal(got[2][:8], got[0])                  # rank 0's rows: its weights and inputs do not depend on the world size
 
 
 def test_failing_rank_fails_the_run_with_its_exit_code():

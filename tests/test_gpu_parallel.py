@@ -138,7 +138,7 @@ def test_bench_two_ranks_share_this_gpu_end_to_end(cuda_device):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env.update(PCV_BENCH_REHEARSE="1", PYTHONPATH=root)
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--workload", "resnet18_bs256", "--batch", "32",
-                        "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--inflight", "2"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                        "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--inflight", "2", "--full"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                        text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -165,7 +165,7 @@ def test_bench_two_gpus_real_rccl(cuda_device):
     env.update(PYTHONPATH=root, PCV_BENCH_TIMEOUT_S="500")
     for extra, batch in ((["--batch", "32"], 64), (["--scaling", "strong", "--global-batch", "64"], 64)):
         p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--workload", "resnet18_bs256", "--steps", "3",
-                            "--warmup", "1", "--no-cpu-baseline"] + extra, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                            "--warmup", "1", "--no-cpu-baseline", "--full"] + extra, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                            text=True, timeout=600)
         assert p.returncode == 0, p.stderr[-2000:]
         out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])

@@ -161,9 +161,12 @@ def test_abi_planner_under_asan_ubsan():
     rt = subprocess.check_output([clang, "-print-file-name=libclang_rt.asan-x86_64.so"], text=True).strip()
     if not os.path.exists(rt):
         pytest.skip("clang's shared ASan runtime not found")
+    # host code only, on any machine: with a GPU visible, HIP's initialisation would allocate device memory through ASan's HSA
+    # interceptors (GPU ASan, which this test is not); hidden from the runtime, the child sees what a CPU-only machine shows
     p = subprocess.run([sys.executable, "-c", _PLAN_CHILD, ROOT, os.path.join(CSRC, "libpcv_host_asan.so")],
                        env=dict(os.environ, LD_PRELOAD=rt, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1:halt_on_error=1",
-                                UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1"),
+                                UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1", ROCR_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="-1",
+                                CUDA_VISIBLE_DEVICES="-1"),
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
     assert p.returncode == 0, "sanitizer report / failed check:\n" + p.stderr[-4000:]
     seen = json.loads(p.stdout.strip().splitlines()[-1])

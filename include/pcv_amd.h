@@ -31,8 +31,9 @@ extern "C" {
  * another layout is refused with PCV_ERR_INVALID instead of being read past its end)
  * 3: + pcv_fp16_guard_begin / pcv_fp16_guard_end / pcv_fp16_overflow_count, + pcv_rccl_* (no layout change)
  * 4: no signature or struct change; the packed-weight blobs of 16-bit depthwise 3x3 layers and of the dense layers listed at
- *    pcv_conv_pack carry a second table, so a blob packed by a version-3 library is too short (size blobs with *_packed_bytes) */
-#define PCV_ABI_VERSION 4
+ *    pcv_conv_pack carry a second table, so a blob packed by a version-3 library is too short (size blobs with *_packed_bytes)
+ * 5: + split attention (pcv_splat_squeeze / _excite / _combine) and padded average pool (pcv_avgpool2d_pad); no layout change */
+#define PCV_ABI_VERSION 5
 
 typedef struct pcv_ctx pcv_ctx;
 
@@ -221,6 +222,29 @@ int pcv_se_excite(pcv_ctx* ctx, const float* mean, const float* w1, const float*
 /* y = post_act(x * gate[n,c] + residual) (att.py:104 + seresnet.py:69-71); residual may be NULL. */
 int pcv_se_scale(pcv_ctx* ctx, const void* x, const float* gate, const void* residual, void* y,
                  int N, int HW, int C, int post_act, int dtype, void* stream);
+
+/* Split attention: SABlock.forward (common/att.py:172-189; ResNeSt's saconv3x3_block, att.py:192-296) and SKConvBlock.forward
+ * (sknet.py:68-83). x is the NHWC output of the split convolution(s), [N, HW, radix * C]: split r is channels [r C, (r + 1) C).
+ * Three launches, all fp32 in between, every reduction per image in a fixed order (an image's result never depends on the batch):
+ *   squeeze  s[N, C] = mean_HW(sum_r x_r)                                   (att.py:174-176; radix 1 = pcv_se_squeeze, same bits)
+ *   excite   mid[N, M] = relu(W1 . s + b1); logits[N, radix C] = W2 . mid + b2 (att.py:178-182 with the BatchNorm folded into
+ *            W1 / b1 by the caller; sknet.py:75-76: pass zero biases); att[N, radix C] = softmax over r of the logit of split r,
+ *            channel c = g Cg + j (Cg = C / groups) taken at index g radix Cg + r Cg + j (att.py:183-185; SKNet: groups = 1) and
+ *            stored radix-major (att[n][r C + c]). `mid` and `logits` are caller-provided fp32 storage (N M and N radix C floats).
+ *   combine  y[N, HW, C] = post_act(sum_r att[n][r C + c] * x_r + residual) (att.py:186-188; residual may be NULL - the unit's
+ *            `x + identity` and ReLU, resnesta.py:196-198), fp32 accumulation, one rounding, fp16 range-guarded.
+ * C % 8 == 0, 1 <= radix <= 4, C % groups == 0; anything else is PCV_ERR_INVALID. */
+int pcv_splat_squeeze(pcv_ctx* ctx, const void* x, float* s, int N, int HW, int C, int radix, int dtype, void* stream);
+int pcv_splat_excite(pcv_ctx* ctx, const float* s, const float* w1, const float* b1, const float* w2, const float* b2, float* mid,
+                     float* logits, float* att, int N, int C, int M, int radix, int groups, void* stream);
+int pcv_splat_combine(pcv_ctx* ctx, const void* x, const float* att, const void* residual, void* y, int N, int HW, int C, int radix,
+                      int post_act, int dtype, void* stream);
+/* nn.AvgPool2d(k, s, p, ceil_mode, count_include_pad) on NHWC (resnesta.py:45-48: (3, s, 1); resnesta.py:138-142: (s, s, 0,
+ * ceil_mode=True, count_include_pad=False)): output size by PyTorch's rule (with ceil_mode the last window must start inside the
+ * input or the left padding), divisor by PyTorch's two rules, fp32 accumulation; p <= k / 2. With p = 0 and no overhang the bits
+ * are pcv_avgpool2d's. */
+int pcv_avgpool2d_pad(pcv_ctx* ctx, const void* x, void* y, int N, int H, int W, int C, int k, int s, int p, int ceil_mode,
+                      int count_include_pad, int dtype, int out_dtype, void* stream);
 
 /* Two chained 1x1 ConvBlocks in one launch: y1 = post_act1(act1(conv1(x)*s1+b1) + residual) - the last convolution of a
  * bottleneck unit with its skip add (resnet.py:227-228) - and y2 = act2(conv2(y1)*s2+b2), the first convolution of the NEXT

@@ -24,7 +24,7 @@ class PcvError(RuntimeError):
         self.code = code
 
 
-PCV_ABI_VERSION = 4
+PCV_ABI_VERSION = 5
 
 
 class ConvDesc(ctypes.Structure):
@@ -94,6 +94,10 @@ _SIGS = {
                               _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "pcv_bn_act": (_I, [_VP, _VP, _VP, _VP, _VP, ctypes.c_long, _I, _I, _I, _I, _VP]),
     "pcv_se_scale": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _VP]),
+    "pcv_splat_squeeze": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _VP]),
+    "pcv_splat_excite": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _VP]),
+    "pcv_splat_combine": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP]),
+    "pcv_avgpool2d_pad": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _VP]),
 }
 
 _lib = None

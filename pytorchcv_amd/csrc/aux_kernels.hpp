@@ -200,42 +200,66 @@ __global__ __launch_bounds__(256) void maxpool_kernel(const void* __restrict__ x
     store8<DT>(y, (size_t)i * 8, m);
 }
 
-// nn.AvgPool2d(k, stride=s) without padding (resnet.py:316-318); general (non-global) case
+// nn.AvgPool2d(k, stride=s, padding=p, ceil_mode, count_include_pad) (resnet.py:316-318 without padding; resnesta.py:45-48
+// (3, s, 1) and :138-142 (s, s, ceil_mode, count_include_pad=False) with it); general (non-global) case. Taps outside the map
+// are skipped; the divisor is PyTorch's: with count_include_pad the window clipped to the padded map, else to the map itself.
+// Without padding or overhang both rules give k * k and the arithmetic is the unpadded kernel's (sum in tap order, times 1 / (k k)).
 template <int DT, int OT>
 __global__ __launch_bounds__(256) void avgpool_kernel(const void* __restrict__ x, void* __restrict__ y, int N, int H, int W,
-                                                     int C, int Ho, int Wo, int k, int s) {
+                                                     int C, int Ho, int Wo, int k, int s, int pad = 0, int count_pad = 1,
+                                                     uint32_t* __restrict__ ovf = nullptr) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     const int C8 = C / 8;
     const long total = (long)N * Ho * Wo * C8;
-    if (i >= total) return;
-    const int c0 = (int)(i % C8) * 8;
-    long t = i / C8;
-    const int wo = (int)(t % Wo);
-    t /= Wo;
-    const int ho = (int)(t % Ho);
-    const int n = (int)(t / Ho);
-    float a[8];
+    F16Guard<OT> guard;
+    if (i < total) {
+        const int c0 = (int)(i % C8) * 8;
+        long t = i / C8;
+        const int wo = (int)(t % Wo);
+        t /= Wo;
+        const int ho = (int)(t % Ho);
+        const int n = (int)(t / Ho);
+        const int h0 = ho * s - pad, w0 = wo * s - pad;
+        float a[8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) a[e] = 0.f;
-    for (int r = 0; r < k; ++r)
-        for (int q = 0; q < k; ++q) {
-            float v[8];
-            load8<DT>(x, (((size_t)n * H + ho * s + r) * W + wo * s + q) * C + c0, v);
+        for (int e = 0; e < 8; ++e) a[e] = 0.f;
+        for (int r = 0; r < k; ++r) {
+            const int hi = h0 + r;
+            if ((unsigned)hi >= (unsigned)H) continue;
+            for (int q = 0; q < k; ++q) {
+                const int wi = w0 + q;
+                if ((unsigned)wi >= (unsigned)W) continue;
+                float v[8];
+                load8<DT>(x, (((size_t)n * H + hi) * W + wi) * C + c0, v);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) a[e] += v[e];
+                for (int e = 0; e < 8; ++e) a[e] += v[e];
+            }
         }
-    const float inv = 1.f / (float)(k * k);
+        int div;
+        if (count_pad) {
+            div = (min(h0 + k, H + pad) - h0) * (min(w0 + k, W + pad) - w0);
+        } else {
+            div = (min(h0 + k, H) - max(h0, 0)) * (min(w0 + k, W) - max(w0, 0));
+        }
+        const float inv = 1.f / (float)div;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) a[e] *= inv;
-    store8<OT>(y, (size_t)i * 8, a);
+        for (int e = 0; e < 8; ++e) a[e] *= inv;
+        guard.see(a);
+        store8<OT>(y, (size_t)i * 8, a);
+    }
+    if (ovf != nullptr) guard.commit(ovf);
 }
 
 // Spatial mean over HW positions: global average pool (AvgPool2d(7) on a 7x7 map, resnet.py:316-318; AdaptiveAvgPool2d(1),
 // efficientnet.py:339) and the SE squeeze (att.py:95). One 512-thread block per (image, group of <= 512 channel chunks):
 // the threads tile [rows x chunks] so that a block reads one contiguous span of the NHWC map per iteration whatever the
 // channel count (C = 32 keeps all 512 threads busy, 128 rows at a time), fp32 accumulation, rows meet in LDS.
+// `radix` R > 1 is the split-attention squeeze (att.py:172-175: mean_HW of the sum of the R splits): x has R * C channels per
+// pixel and each row adds its R splits into the running sum in split order; R = 1 is the plain mean, the same operations.
+// An image's result depends on that image only, in a fixed order: no atomics, no cross-block reduction.
 template <int DT, int OT>
-__global__ __launch_bounds__(512) void spatial_mean_kernel(const void* __restrict__ x, void* __restrict__ y, int HW, int C) {
+__global__ __launch_bounds__(512) void spatial_mean_kernel(const void* __restrict__ x, void* __restrict__ y, int HW, int C,
+                                                          int radix = 1) {
     __shared__ float part[512][9];                       // +1: the row-sum reads below walk it with a stride of Gc rows
     const int n = blockIdx.x;
     const int C8 = C >> 3;
@@ -248,13 +272,26 @@ __global__ __launch_bounds__(512) void spatial_mean_kernel(const void* __restric
 #pragma unroll
     for (int e = 0; e < 8; ++e) a[e] = 0.f;
     if (r < R) {
-        const size_t base = (size_t)n * HW * C + (size_t)(g0 + c) * 8;
+        const size_t RC = (size_t)radix * C;
+        const size_t base = (size_t)n * HW * RC + (size_t)(g0 + c) * 8;
+        if (radix == 1) {
 #pragma unroll 4
-        for (int hw = r; hw < HW; hw += R) {
-            float v[8];
-            load8<DT>(x, base + (size_t)hw * C, v);
+            for (int hw = r; hw < HW; hw += R) {
+                float v[8];
+                load8<DT>(x, base + (size_t)hw * C, v);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) a[e] += v[e];
+                for (int e = 0; e < 8; ++e) a[e] += v[e];
+            }
+        } else {
+#pragma unroll 2
+            for (int hw = r; hw < HW; hw += R) {
+                for (int s = 0; s < radix; ++s) {
+                    float v[8];
+                    load8<DT>(x, base + (size_t)hw * RC + (size_t)s * C, v);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) a[e] += v[e];
+                }
+            }
         }
     }
 #pragma unroll
@@ -368,6 +405,77 @@ __global__ __launch_bounds__(256) void se_scale_kernel(const void* __restrict__ 
         if (post_act != PCV_ACT_NONE) apply_act8(v, pact);
         guard.see(v);
         store8<DT>(y, (size_t)i * 8, v);
+    }
+    guard.commit(ovf);
+}
+
+// ---- split attention (att.py:172-189, sknet.py:59-83) ----------------------------------------------------------------------
+// rSoftMax: the second excitation layer's logits [N][R * C] are laid out (groups, R, C / groups) per image (att.py:183-185: viewed
+// as (N, groups, R, Cg), transposed to (N, R, groups, Cg)); att[n][r * C + c] = softmax over r of logit[n][g R Cg + r Cg + j] with
+// c = g Cg + j - stored radix-major, so the combine reads a_r for 8 consecutive channels as one 32-byte vector. fp32, max-subtracted.
+__global__ __launch_bounds__(256) void splat_softmax_kernel(const float* __restrict__ logit, float* __restrict__ att, int N, int C,
+                                                           int R, int Cg) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;        // over N * C
+    if (i >= (long)N * C) return;
+    const int c = (int)(i % C);
+    const long n = i / C;
+    const int g = c / Cg, j = c - g * Cg;
+    const float* l = logit + (size_t)n * R * C + (size_t)g * R * Cg + j;
+    float v[4];                                                  // R <= 4 (checked by the entry point); unrolled: no scratch
+    float m = l[0];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        v[r] = r < R ? l[(size_t)r * Cg] : 0.f;
+        if (r < R) m = fmaxf(m, v[r]);
+    }
+    float sum = 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        v[r] = expf(v[r] - m);
+        if (r < R) sum += v[r];
+    }
+    const float inv = 1.f / sum;
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+        if (r < R) att[(size_t)n * R * C + (size_t)r * C + c] = v[r] * inv;
+}
+
+// y = post_act(sum_r att[n][r C + c] * x[n, p, r C + c] + residual[n, p, c]) (att.py:187-188 / sknet.py:81-82, and the unit's
+// `x + identity` + ReLU, resnesta.py:196-198): x [N, HW, R * C], y / residual [N, HW, C]; fp32 accumulation in split order, one
+// rounding. One thread = 8 output channels of one pixel; fresh blocks (grid-stride only under the test cap, as se_scale_kernel).
+template <int DT>
+__global__ __launch_bounds__(256) void splat_combine_kernel(const void* __restrict__ x, const float* __restrict__ att,
+                                                           const void* __restrict__ res, void* __restrict__ y, long total8, int HW,
+                                                           int C, int R, int post_act, uint32_t* __restrict__ ovf) {
+    const int C8 = C / 8;
+    const ActClamp pact = make_act(post_act);
+    F16Guard<DT> guard;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total8; i += (long)gridDim.x * 256) {
+        const int c0 = (int)(i % C8) * 8;
+        const long pix = i / C8;
+        const long n = pix / HW;
+        const size_t xb = (size_t)pix * R * C + c0;
+        const float* ab = att + (size_t)n * R * C + c0;
+        float acc[8], v[8], g[8];
+        load8<DT>(x, xb, v);
+        load8<PCV_F32>(ab, 0, g);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[e] = g[e] * v[e];
+        for (int r = 1; r < R; ++r) {
+            load8<DT>(x, xb + (size_t)r * C, v);
+            load8<PCV_F32>(ab, (size_t)r * C, g);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[e] = fmaf(g[e], v[e], acc[e]);
+        }
+        if (res != nullptr) {
+            float q[8];
+            load8<DT>(res, (size_t)i * 8, q);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[e] += q[e];
+        }
+        if (post_act != PCV_ACT_NONE) apply_act8(acc, pact);
+        guard.see(acc);
+        store8<DT>(y, (size_t)i * 8, acc);
     }
     guard.commit(ovf);
 }

@@ -821,17 +821,19 @@ template <int DT> static void launch_dw(const pcv_conv_desc& d, const DwParams& 
     if (d.act <= PCV_ACT_RELU6 && d.post_act <= PCV_ACT_RELU6) launch_dw2<DT, true>(d, p, grid, s);
     else launch_dw2<DT, false>(d, p, grid, s);
 }
-template <int DT> static void launch_mean(const void* x, void* y, int N, int HW, int C, int ot, hipStream_t s) {
+// `radix` > 1: the split-attention squeeze over x with radix * C channels per pixel (pcv_splat_squeeze)
+template <int DT> static void launch_mean(const void* x, void* y, int N, int HW, int C, int ot, hipStream_t s, int radix = 1) {
     dim3 grid((unsigned)N, (unsigned)((C / 8 + 511) / 512));
-    if (ot == PCV_F32) spatial_mean_kernel<DT, PCV_F32><<<grid, 512, 0, s>>>(x, y, HW, C);
-    else spatial_mean_kernel<DT, DT><<<grid, 512, 0, s>>>(x, y, HW, C);
+    if (ot == PCV_F32) spatial_mean_kernel<DT, PCV_F32><<<grid, 512, 0, s>>>(x, y, HW, C, radix);
+    else spatial_mean_kernel<DT, DT><<<grid, 512, 0, s>>>(x, y, HW, C, radix);
 }
+// `pad` / `count_pad` / `ovf`: the padded pool of pcv_avgpool2d_pad (pcv_avgpool2d: no padding, no range counting)
 template <int DT> static void launch_avg(const void* x, void* y, int N, int H, int W, int C, int Ho, int Wo, int k, int s,
-                                         int ot, hipStream_t st) {
+                                         int ot, hipStream_t st, int pad = 0, int count_pad = 1, uint32_t* ovf = nullptr) {
     const long total = (long)N * Ho * Wo * (C / 8);
     const unsigned grid = (unsigned)((total + 255) / 256);
-    if (ot == PCV_F32) avgpool_kernel<DT, PCV_F32><<<grid, 256, 0, st>>>(x, y, N, H, W, C, Ho, Wo, k, s);
-    else avgpool_kernel<DT, DT><<<grid, 256, 0, st>>>(x, y, N, H, W, C, Ho, Wo, k, s);
+    if (ot == PCV_F32) avgpool_kernel<DT, PCV_F32><<<grid, 256, 0, st>>>(x, y, N, H, W, C, Ho, Wo, k, s, pad, count_pad, ovf);
+    else avgpool_kernel<DT, DT><<<grid, 256, 0, st>>>(x, y, N, H, W, C, Ho, Wo, k, s, pad, count_pad, ovf);
 }
 
 
@@ -1985,6 +1987,75 @@ int pcv_se_scale(pcv_ctx* ctx, const void* x, const float* gate, const void* res
     if (dtype == PCV_BF16) se_scale_kernel<PCV_BF16><<<(unsigned)blocks, 256, 0, st>>>(x, gate, residual, y, total8, HW, C, post_act, ctx->ovf);
     else if (dtype == PCV_F16) se_scale_kernel<PCV_F16><<<(unsigned)blocks, 256, 0, st>>>(x, gate, residual, y, total8, HW, C, post_act, ctx->ovf);
     else se_scale_kernel<PCV_F32><<<(unsigned)blocks, 256, 0, st>>>(x, gate, residual, y, total8, HW, C, post_act, ctx->ovf);
+    HIP_TRY(ctx, hipGetLastError());
+    return PCV_OK;
+}
+
+// ---- split attention (att.py:172-189, sknet.py:59-83) and the padded average pool (resnesta.py:45-48,138-142) ---------------
+int pcv_splat_squeeze(pcv_ctx* ctx, const void* x, float* s, int N, int HW, int C, int radix, int dtype, void* stream) {
+    if (!ctx) return PCV_ERR_INVALID;
+    DeviceGuard device_guard(ctx->device);
+    if (!x || !s || N <= 0 || HW <= 0 || C <= 0 || C % 8 != 0 || radix < 1 || radix > 4 || !dtype_ok(dtype))
+        return fail(ctx, PCV_ERR_INVALID, "pcv_splat_squeeze: bad argument (C must be a multiple of 8, radix in [1, 4])");
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == PCV_BF16) launch_mean<PCV_BF16>(x, s, N, HW, C, PCV_F32, st, radix);
+    else if (dtype == PCV_F16) launch_mean<PCV_F16>(x, s, N, HW, C, PCV_F32, st, radix);
+    else launch_mean<PCV_F32>(x, s, N, HW, C, PCV_F32, st, radix);
+    HIP_TRY(ctx, hipGetLastError());
+    return PCV_OK;
+}
+
+int pcv_splat_excite(pcv_ctx* ctx, const float* s, const float* w1, const float* b1, const float* w2, const float* b2, float* mid,
+                     float* logits, float* att, int N, int C, int M, int radix, int groups, void* stream) {
+    if (!ctx) return PCV_ERR_INVALID;
+    DeviceGuard device_guard(ctx->device);
+    if (!s || !w1 || !b1 || !w2 || !b2 || !mid || !logits || !att || N <= 0 || C <= 0 || C % 8 != 0 || M <= 0 || radix < 1 ||
+        radix > 4 || groups < 1 || C % groups != 0)
+        return fail(ctx, PCV_ERR_INVALID, "pcv_splat_excite: bad argument (C must be a multiple of 8 and of groups, radix in [1, 4])");
+    hipStream_t st = (hipStream_t)stream;
+    launch_se_fc(s, w1, b1, mid, N, C, M, PCV_ACT_RELU, st);
+    launch_se_fc(mid, w2, b2, logits, N, M, radix * C, PCV_ACT_NONE, st);
+    const long total = (long)N * C;
+    splat_softmax_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(logits, att, N, C, radix, C / groups);
+    HIP_TRY(ctx, hipGetLastError());
+    return PCV_OK;
+}
+
+int pcv_splat_combine(pcv_ctx* ctx, const void* x, const float* att, const void* residual, void* y, int N, int HW, int C, int radix,
+                      int post_act, int dtype, void* stream) {
+    if (!ctx) return PCV_ERR_INVALID;
+    DeviceGuard device_guard(ctx->device);
+    if (!x || !att || !y || N <= 0 || HW <= 0 || C <= 0 || C % 8 != 0 || radix < 1 || radix > 4 || !dtype_ok(dtype) ||
+        post_act < PCV_ACT_NONE || post_act > PCV_ACT_HSWISH)
+        return fail(ctx, PCV_ERR_INVALID, "pcv_splat_combine: bad argument (C must be a multiple of 8, radix in [1, 4])");
+    const long total8 = (long)N * HW * (C / 8);
+    long blocks = (total8 + 255) / 256;
+    if (ctx->max_blocks > 0 && blocks > ctx->max_blocks) blocks = ctx->max_blocks;      // multi-round tests only (as pcv_se_scale)
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == PCV_BF16)
+        splat_combine_kernel<PCV_BF16><<<(unsigned)blocks, 256, 0, st>>>(x, att, residual, y, total8, HW, C, radix, post_act, ctx->ovf);
+    else if (dtype == PCV_F16)
+        splat_combine_kernel<PCV_F16><<<(unsigned)blocks, 256, 0, st>>>(x, att, residual, y, total8, HW, C, radix, post_act, ctx->ovf);
+    else splat_combine_kernel<PCV_F32><<<(unsigned)blocks, 256, 0, st>>>(x, att, residual, y, total8, HW, C, radix, post_act, ctx->ovf);
+    HIP_TRY(ctx, hipGetLastError());
+    return PCV_OK;
+}
+
+int pcv_avgpool2d_pad(pcv_ctx* ctx, const void* x, void* y, int N, int H, int W, int C, int k, int s, int p, int ceil_mode,
+                      int count_include_pad, int dtype, int out_dtype, void* stream) {
+    if (!ctx) return PCV_ERR_INVALID;
+    DeviceGuard device_guard(ctx->device);
+    if (!x || !y || N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 != 0 || k <= 0 || s <= 0 || p < 0 || 2 * p > k ||
+        !dtype_ok(dtype) || (out_dtype != dtype && out_dtype != PCV_F32))
+        return fail(ctx, PCV_ERR_INVALID, "pcv_avgpool2d_pad: bad argument (C must be a multiple of 8, pad <= k/2)");
+    if (H + 2 * p < k || W + 2 * p < k) return fail(ctx, PCV_ERR_INVALID, "pcv_avgpool2d_pad: window wider than the padded map");
+    const int Ho = pool_out(H, k, s, p, ceil_mode), Wo = pool_out(W, k, s, p, ceil_mode);
+    if (Ho <= 0 || Wo <= 0) return fail(ctx, PCV_ERR_INVALID, "pcv_avgpool2d_pad: empty output");
+    hipStream_t st = (hipStream_t)stream;
+    const int cp = count_include_pad ? 1 : 0;
+    if (dtype == PCV_BF16) launch_avg<PCV_BF16>(x, y, N, H, W, C, Ho, Wo, k, s, out_dtype, st, p, cp, ctx->ovf);
+    else if (dtype == PCV_F16) launch_avg<PCV_F16>(x, y, N, H, W, C, Ho, Wo, k, s, out_dtype, st, p, cp, ctx->ovf);
+    else launch_avg<PCV_F32>(x, y, N, H, W, C, Ho, Wo, k, s, out_dtype, st, p, cp, ctx->ovf);
     HIP_TRY(ctx, hipGetLastError());
     return PCV_OK;
 }

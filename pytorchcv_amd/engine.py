@@ -5,7 +5,7 @@
 """
 
 __all__ = ['NHWC', 'DTYPES', 'default_dtype', 'set_compute_dtype', 'compute_dtype_of', 'Fp16Guard', 'fp16_overflow_count', 'from_nchw', 'to_nchw', 'ConvRunner',
-           'BnActRunner', 'maxpool2d', 'avgpool2d', 'global_avgpool', 'se_forward', 'channel_slice', 'cat_shuffle2', 'act_code',
+           'BnActRunner', 'maxpool2d', 'avgpool2d', 'avgpool2d_pad', 'global_avgpool', 'se_forward', 'splat_forward', 'channel_slice', 'cat_shuffle2', 'act_code',
            'boundary', 'round8', 'channel_concat_into', 'interpolate', 'add']
 
 import os
@@ -689,6 +689,22 @@ def avgpool2d(x: NHWC, k: int, s: int, out_fp32: bool = False) -> NHWC:
     return NHWC(y, x.N, Ho, Wo, x.C, cpitch=x.cpitch)
 
 
+def avgpool2d_pad(x: NHWC, k: int, s: int, p: int = 0, ceil_mode: bool = False, count_include_pad: bool = True) -> NHWC:
+    """nn.AvgPool2d(k, s, p, ceil_mode, count_include_pad) on an NHWC handle (pcv_avgpool2d_pad): ResNeSt's padded 3x3 pool and
+    its ceil-mode identity pool (reference resnesta.py:45-48,138-142)."""
+    if not x.dense:
+        raise RuntimeError("avg-pool on a padded handle")
+    Ho, Wo = _pool_out(x.H, k, s, p, ceil_mode), _pool_out(x.W, k, s, p, ceil_mode)
+    if Ho <= 0 or Wo <= 0:
+        raise RuntimeError("AvgPool2d({}, {}, {}) output of a {}x{} map would be empty".format(k, s, p, x.H, x.W))
+    y = torch.empty((x.N, Ho, Wo, x.cpitch), dtype=x.dtype, device=x.device)
+    ctx = _ctx(x.device)
+    code = _CODE_OF_TORCH[x.dtype]
+    _lib.check(_lib.lib().pcv_avgpool2d_pad(ctx, _ptr(x.t), _ptr(y), x.N, x.H, x.W, x.cpitch, k, s, p, 1 if ceil_mode else 0,
+                                            1 if count_include_pad else 0, code, code, _stream(x.device)), ctx)
+    return NHWC(y, x.N, Ho, Wo, x.C, cpitch=x.cpitch)
+
+
 # The classifier head runs in fp32: the `final_pool` of a net writes fp32 pooled features and the classifier behind it (Linear /
 # 1x1 convolutions on the 1 x 1 map: 2-3 MMAC per image, nothing) runs on the exact-f32 MFMA path with fp32 weights. Measured on the
 # golden fixtures (tests/tools/bf16_drift.py): everything in front of the global pool is averaged over the 49 positions of the last
@@ -855,3 +871,31 @@ def se_forward(x: NHWC, w1, b1, w2, b2, mid_act: int, out_act: int, residual: NH
     _lib.check(L.pcv_se_scale(ctx, _ptr(x.t), _ptr(gate), _ptr(residual.t) if residual is not None else None, _ptr(y),
                               x.N, x.H * x.W, CP, post_act, code, st), ctx)
     return NHWC(y, x.N, x.H, x.W, x.C, cpitch=CP)
+
+
+def splat_forward(x: NHWC, radix: int, groups: int, w1, b1, w2, b2, residual: NHWC | None = None, post_act: int = 0) -> NHWC:
+    """Split attention on the hot path (SABlock, reference att.py:172-189; SKConvBlock, sknet.py:68-83): squeeze the sum of the
+    `radix` splits of x [N, H, W, radix * C] -> fp32 MLP (w1 [M, C], b1 [M] with the MLP's BatchNorm folded in; w2 [radix C, M],
+    b2 [radix C]) -> softmax across the splits -> per-channel weighted sum of the splits (+ residual, + activation): three
+    launches, the result is [N, H, W, C]."""
+    if not x.dense or x.C % radix:
+        raise RuntimeError("split attention needs a dense handle whose channels split into {} parts".format(radix))
+    C = x.C // radix
+    if C % 8:
+        raise NotImplementedError("split attention with {} channels per split: the MI355X path needs multiples of 8".format(C))
+    L, ctx, st = _lib.lib(), _ctx(x.device), _stream(x.device)
+    code = _CODE_OF_TORCH[x.dtype]
+    N, HW, M = x.N, x.H * x.W, int(w1.shape[0])
+    s = torch.empty((N, C), dtype=torch.float32, device=x.device)
+    _lib.check(L.pcv_splat_squeeze(ctx, _ptr(x.t), _ptr(s), N, HW, C, radix, code, st), ctx)
+    mid = torch.empty((N, M), dtype=torch.float32, device=x.device)
+    logits = torch.empty((N, radix * C), dtype=torch.float32, device=x.device)
+    att = torch.empty((N, radix * C), dtype=torch.float32, device=x.device)
+    _lib.check(L.pcv_splat_excite(ctx, _ptr(s), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(mid), _ptr(logits), _ptr(att), N, C, M,
+                                  radix, groups, st), ctx)
+    y = torch.empty((N, x.H, x.W, C), dtype=x.dtype, device=x.device)
+    if residual is not None and (tuple(residual.t.shape) != tuple(y.shape) or residual.dtype != x.dtype):
+        raise RuntimeError("split-attention residual shape/dtype mismatch: {} vs {}".format(tuple(residual.t.shape), tuple(y.shape)))
+    _lib.check(L.pcv_splat_combine(ctx, _ptr(x.t), _ptr(att), _ptr(residual.t) if residual is not None else None, _ptr(y), N, HW,
+                                   C, radix, post_act, code, st), ctx)
+    return NHWC(y, N, x.H, x.W, C)

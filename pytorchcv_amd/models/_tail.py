@@ -3,7 +3,7 @@
     nn.AvgPool2d (same attribute names, no state), the classifier tail and the pretrained-weights hook of every factory.
 """
 
-__all__ = ['MaxPool2dNHWC', 'AvgPool2dNHWC', 'GlobalAvgPool2dNHWC', 'LinearHead', 'run_net', 'check_channels', 'maybe_load_pretrained', 'init_conv_params']
+__all__ = ['MaxPool2dNHWC', 'AvgPool2dNHWC', 'AvgPool2dPadNHWC', 'GlobalAvgPool2dNHWC', 'LinearHead', 'run_net', 'check_channels', 'maybe_load_pretrained', 'init_conv_params']
 
 import os
 import torch
@@ -32,6 +32,20 @@ class AvgPool2dNHWC(nn.Module):
     def forward(self, x):
         head = engine.FP32_HEAD and self.fp32_out and isinstance(x, engine.NHWC)
         return engine.boundary(self, x, lambda a: engine.avgpool2d(a, self.kernel_size, self.stride, out_fp32=head))
+
+
+class AvgPool2dPadNHWC(nn.Module):
+    """nn.AvgPool2d(kernel_size, stride, padding, ceil_mode, count_include_pad) (reference resnesta.py:45-48,138-142) ->
+    pcv_avgpool2d_pad; the map stays in the storage type."""
+    def __init__(self, kernel_size, stride=None, padding=0, ceil_mode=False, count_include_pad=True):
+        super(AvgPool2dPadNHWC, self).__init__()
+        self.kernel_size = int(kernel_size)
+        self.stride = int(stride) if stride is not None else self.kernel_size
+        self.padding, self.ceil_mode, self.count_include_pad = int(padding), bool(ceil_mode), bool(count_include_pad)
+
+    def forward(self, x):
+        return engine.boundary(self, x, lambda a: engine.avgpool2d_pad(a, self.kernel_size, self.stride, self.padding, self.ceil_mode,
+                                                                       self.count_include_pad))
 
 
 class GlobalAvgPool2dNHWC(nn.Module):

@@ -2,13 +2,17 @@
     Squeeze-and-Excitation (reference pytorchcv/models/common/att.py:15-105): same attributes (`conv1`/`conv2` with bias, or
     `fc1`/`fc2`), three small launches on the hot path: spatial mean -> fp32 excitation MLP -> channel scale fused with the
     unit's residual add and activation.
+    Split attention (att.py:108-296: SABlock, SAConvBlock, saconv3x3_block): the same three-launch shape across the radix splits
+    of one convolution's output - squeeze of their sum -> fp32 MLP + softmax over the splits -> weighted sum of the splits.
 """
 
-__all__ = ['round_channels', 'SEBlock']
+__all__ = ['round_channels', 'SEBlock', 'SABlock', 'SAConvBlock', 'saconv3x3_block', 'fold_bn_into_fc']
 
+import torch
 import torch.nn as nn
 from .activ import lambda_relu, lambda_sigmoid, create_activation_layer
-from .conv import conv1x1
+from .conv import conv1x1, ConvBlock
+from .norm import lambda_batchnorm2d, create_normalization_layer
 from ... import engine
 
 
@@ -77,3 +81,94 @@ class SEBlock(nn.Module):
         w1, b1, w2, b2 = self._mlp()
         return engine.boundary(self, x, lambda a: engine.se_forward(
             a, w1, b1, w2, b2, engine.act_code(self.activ), engine.act_code(self.sigmoid), residual, engine.act_code(post_act)))
+
+
+def fold_bn_into_fc(w, b, bn):
+    """(w [M, K], b [M] or None) of a 1x1 layer followed by the eval-mode BatchNorm2d `bn` -> fp32 (w', b') of the composed affine
+    map: w' = w * g / sqrt(var + eps) (per row), b' = (b - mean) * g / sqrt(var + eps) + beta."""
+    w = w.detach().float().reshape(w.shape[0], -1)
+    b = b.detach().float() if b is not None else torch.zeros(w.shape[0], dtype=torch.float32, device=w.device)
+    if bn is None:
+        return w.contiguous(), b.contiguous()
+    if bn.training:
+        raise RuntimeError("pytorchcv_amd is an inference path: call net.eval() first (BatchNorm is folded)")
+    g = bn.weight.detach().float() if bn.weight is not None else torch.ones_like(b)
+    beta = bn.bias.detach().float() if bn.bias is not None else torch.zeros_like(b)
+    sc = g / torch.sqrt(bn.running_var.detach().float() + bn.eps)
+    return (w * sc[:, None]).contiguous(), ((b - bn.running_mean.detach().float()) * sc + beta).contiguous()
+
+
+class _FoldedMlp(object):
+    """The fp32 (w1, b1, w2, b2) of a split-attention MLP, re-derived whenever a source parameter changes (load_state_dict, .to())."""
+    def __init__(self):
+        self.key, self.value = None, None
+
+    def get(self, sources, build):
+        key = tuple((t.data_ptr(), t._version) if t is not None else None for t in sources)
+        if key != self.key:
+            self.value, self.key = build(), key
+        return self.value
+
+
+class SABlock(nn.Module):
+    """Split-attention block (reference att.py:108-189): same constructor, same attributes (`pool`, `conv1`/`fc1`, `bn`, `activ`,
+    `conv2`/`fc2`, `softmax`). `forward(x, residual=None, post_act=None)` also takes the unit's skip tensor and the activation after
+    the add (ResNeSt-A's basic block ends in this block, resnesta.py:196-198): they ride in the combine launch."""
+    def __init__(self, out_channels, groups, radix, reduction=4, min_channels=32, use_conv=True,
+                 normalization=lambda_batchnorm2d()):
+        super(SABlock, self).__init__()
+        self.groups = groups
+        self.radix = radix
+        self.use_conv = use_conv
+        in_channels = out_channels * radix
+        mid_channels = max(in_channels // reduction, min_channels)
+        self.pool = nn.AdaptiveAvgPool2d(output_size=1)      # marker only; the squeeze kernel computes it
+        if use_conv:
+            self.conv1 = conv1x1(in_channels=out_channels, out_channels=mid_channels, bias=True)
+        else:
+            self.fc1 = nn.Linear(in_features=out_channels, out_features=mid_channels)
+        self.bn = create_normalization_layer(normalization=normalization, num_features=mid_channels)
+        self.activ = nn.ReLU(inplace=True)
+        if use_conv:
+            self.conv2 = conv1x1(in_channels=mid_channels, out_channels=in_channels, bias=True)
+        else:
+            self.fc2 = nn.Linear(in_features=mid_channels, out_features=in_channels)
+        self.softmax = nn.Softmax(dim=1)
+        self._pcv_mlp = _FoldedMlp()
+
+    def _mlp(self):
+        a, b = (self.conv1, self.conv2) if self.use_conv else (self.fc1, self.fc2)
+        srcs = [a.weight, a.bias, b.weight, b.bias, self.bn.weight, self.bn.bias, self.bn.running_mean, self.bn.running_var]
+
+        def build():
+            w1, b1 = fold_bn_into_fc(a.weight, a.bias, self.bn)
+            return w1, b1, b.weight.detach().float().reshape(b.weight.shape[0], -1).contiguous(), b.bias.detach().float().contiguous()
+        return self._pcv_mlp.get(srcs, build)
+
+    def _run(self, a, residual=None, post_act=None):
+        w1, b1, w2, b2 = self._mlp()
+        return engine.splat_forward(a, self.radix, self.groups, w1, b1, w2, b2, residual, engine.act_code(post_act))
+
+    def forward(self, x, residual=None, post_act=None):
+        return engine.boundary(self, x, lambda a: self._run(a, residual, post_act))
+
+
+class SAConvBlock(nn.Module):
+    """Split-attention convolution block (reference att.py:192-276): a ConvBlock with `out_channels * radix` outputs in
+    `groups * radix` groups (one fused launch) followed by the SABlock (three launches)."""
+    def __init__(self, in_channels, out_channels, kernel_size, stride, padding, dilation=1, groups=1, bias=False,
+                 normalization=lambda_batchnorm2d(), activation=lambda_relu(), radix=2, reduction=4, min_channels=32,
+                 use_conv=True):
+        super(SAConvBlock, self).__init__()
+        self.conv = ConvBlock(in_channels=in_channels, out_channels=(out_channels * radix), kernel_size=kernel_size, stride=stride,
+                              padding=padding, dilation=dilation, groups=(groups * radix), bias=bias, normalization=normalization,
+                              activation=activation)
+        self.att = SABlock(out_channels=out_channels, groups=groups, radix=radix, reduction=reduction, min_channels=min_channels,
+                           use_conv=use_conv, normalization=normalization)
+
+    def forward(self, x, residual=None, post_act=None):
+        return engine.boundary(self, x, lambda a: self.att(self.conv(a), residual=residual, post_act=post_act))
+
+
+def saconv3x3_block(stride=1, padding=1, **kwargs):
+    return SAConvBlock(kernel_size=3, stride=stride, padding=padding, **kwargs)

@@ -1,0 +1,142 @@
+"""
+    SKNet for ImageNet-1K on the MI355X hot path (reference pytorchcv/models/sknet.py:15-300). Module tree, attribute names and
+    factory signatures follow the reference so its state_dicts load strictly. The selective-kernel block's branches write their
+    channel slices of one [N, H, W, M * C] buffer straight from the convolution epilogue (no stack, no copy, no NCHW), and the
+    selection is the split-attention launches of common/att.py with groups = 1.
+"""
+
+__all__ = ['SKNet', 'sknet50', 'sknet101', 'sknet152', 'SKConvBlock', 'SKNetBottleneck', 'SKNetUnit', 'get_sknet']
+
+import torch
+import torch.nn as nn
+from .common.conv import conv1x1, conv1x1_block, conv3x3_block
+from .common.att import fold_bn_into_fc, _FoldedMlp
+from .resnet import ResInitBlock
+from ._tail import AvgPool2dNHWC, LinearHead, run_net, maybe_load_pretrained, init_conv_params, DEFAULT_ROOT
+from .. import engine
+
+
+class SKConvBlock(nn.Module):
+    """M dilated grouped 3x3 branches + selection (reference sknet.py:15-83). `branches` is a plain container with the reference's
+    child names (branch2, branch3, ...), so the state_dict keys match its `Concurrent(stack=True)`."""
+    def __init__(self, in_channels, out_channels, stride, groups=32, num_branches=2, reduction=16, min_channels=32):
+        super(SKConvBlock, self).__init__()
+        self.num_branches = num_branches
+        self.out_channels = out_channels
+        mid_channels = max(in_channels // reduction, min_channels)
+        self.branches = nn.Sequential()
+        for i in range(num_branches):
+            dilation = 1 + i
+            self.branches.add_module("branch{}".format(i + 2), conv3x3_block(
+                in_channels=in_channels, out_channels=out_channels, stride=stride, padding=dilation, dilation=dilation,
+                groups=groups))
+        self.pool = nn.AdaptiveAvgPool2d(output_size=1)       # marker only; the squeeze kernel computes it
+        self.fc1 = conv1x1_block(in_channels=out_channels, out_channels=mid_channels)
+        self.fc2 = conv1x1(in_channels=mid_channels, out_channels=(out_channels * num_branches))
+        self.softmax = nn.Softmax(dim=1)
+        self._pcv_mlp = _FoldedMlp()
+
+    def _mlp(self):
+        c1, bn, w2 = self.fc1.conv, self.fc1.bn, self.fc2.weight
+        srcs = [c1.weight, c1.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, w2]
+
+        def build():
+            w1, b1 = fold_bn_into_fc(c1.weight, c1.bias, bn)
+            w2f = w2.detach().float().reshape(w2.shape[0], -1).contiguous()
+            return w1, b1, w2f, torch.zeros(w2f.shape[0], dtype=torch.float32, device=w2f.device)
+        return self._pcv_mlp.get(srcs, build)
+
+    def _run(self, a):
+        C, M = self.out_channels, self.num_branches
+        if C % 8:
+            raise NotImplementedError("SKConvBlock with {} channels: the MI355X path needs multiples of 8".format(C))
+        c = self.branches.branch2.conv
+        s, k = c.stride[0], c.kernel_size[0]
+        Ho = (a.H + 2 * c.padding[0] - c.dilation[0] * (k - 1) - 1) // s + 1
+        Wo = (a.W + 2 * c.padding[1] - c.dilation[1] * (k - 1) - 1) // c.stride[1] + 1
+        buf = torch.empty((a.N, Ho, Wo, M * C), dtype=a.dtype, device=a.device)
+        for i, branch in enumerate(self.branches.children()):
+            branch(a, out=(buf, i * C))                       # the convolution writes its channel slice: no stack
+        w1, b1, w2, b2 = self._mlp()
+        return engine.splat_forward(engine.NHWC(buf, a.N, Ho, Wo, M * C), M, 1, w1, b1, w2, b2)
+
+    def forward(self, x):
+        return engine.boundary(self, x, self._run)
+
+
+class SKNetBottleneck(nn.Module):
+    """1x1 -> selective-kernel block -> 1x1 (reference sknet.py:86-130); `residual` / `post_act` ride in conv3's epilogue."""
+    def __init__(self, in_channels, out_channels, stride, bottleneck_factor=2):
+        super(SKNetBottleneck, self).__init__()
+        mid_channels = out_channels // bottleneck_factor
+        self.conv1 = conv1x1_block(in_channels=in_channels, out_channels=mid_channels)
+        self.conv2 = SKConvBlock(in_channels=mid_channels, out_channels=mid_channels, stride=stride)
+        self.conv3 = conv1x1_block(in_channels=mid_channels, out_channels=out_channels, activation=None)
+
+    def forward(self, x, residual=None, post_act=None):
+        return engine.boundary(self, x, lambda a: self.conv3(self.conv2(self.conv1(a)), residual=residual, post_act=post_act))
+
+
+class SKNetUnit(nn.Module):
+    """relu(body(x) + identity) (reference sknet.py:133-176)."""
+    def __init__(self, in_channels, out_channels, stride):
+        super(SKNetUnit, self).__init__()
+        self.resize_identity = (in_channels != out_channels) or (stride != 1)
+        self.body = SKNetBottleneck(in_channels=in_channels, out_channels=out_channels, stride=stride)
+        if self.resize_identity:
+            self.identity_conv = conv1x1_block(in_channels=in_channels, out_channels=out_channels, stride=stride, activation=None)
+        self.activ = nn.ReLU(inplace=True)
+
+    def _run(self, a):
+        identity = self.identity_conv(a) if self.resize_identity else a
+        return self.body(a, residual=identity, post_act=self.activ)
+
+    def forward(self, x):
+        return engine.boundary(self, x, self._run)
+
+
+class SKNet(nn.Module):
+    """`features` (ResInitBlock, stage1..4, final_pool) + `output` Linear (reference sknet.py:179-245)."""
+    pcv_16bit = "fp16"      # the 16-bit mode "auto" resolves to for this family (engine.compute_dtype_of)
+    def __init__(self, channels, init_block_channels, in_channels=3, in_size=(224, 224), num_classes=1000):
+        super(SKNet, self).__init__()
+        self.in_size = in_size
+        self.num_classes = num_classes
+        self.features = nn.Sequential()
+        self.features.add_module("init_block", ResInitBlock(in_channels=in_channels, out_channels=init_block_channels))
+        in_channels = init_block_channels
+        for i, channels_per_stage in enumerate(channels):
+            stage = nn.Sequential()
+            for j, out_channels in enumerate(channels_per_stage):
+                stride = 2 if (j == 0) and (i != 0) else 1
+                stage.add_module("unit{}".format(j + 1), SKNetUnit(in_channels=in_channels, out_channels=out_channels, stride=stride))
+                in_channels = out_channels
+            self.features.add_module("stage{}".format(i + 1), stage)
+        self.features.add_module("final_pool", AvgPool2dNHWC(kernel_size=7, stride=1, fp32_out=True))
+        self.output = LinearHead(in_features=in_channels, out_features=num_classes)
+        init_conv_params(self)
+        engine.stamp_family_dtype(self)                    # sub-modules called on their own resolve "auto" like the net
+
+    def forward(self, x):
+        return run_net(self, x, self.output)
+
+
+def get_sknet(blocks, model_name=None, pretrained=False, root=DEFAULT_ROOT, **kwargs):
+    layers = {50: [3, 4, 6, 3], 101: [3, 4, 23, 3], 152: [3, 8, 36, 3]}.get(blocks)
+    if layers is None:
+        raise ValueError("Unsupported SKNet with number of blocks: {}".format(blocks))
+    channels = [[ci] * li for (ci, li) in zip([256, 512, 1024, 2048], layers)]
+    net = SKNet(channels=channels, init_block_channels=64, **kwargs)
+    return maybe_load_pretrained(net, model_name, pretrained, root)
+
+
+def sknet50(**kwargs):
+    return get_sknet(blocks=50, model_name="sknet50", **kwargs)
+
+
+def sknet101(**kwargs):
+    return get_sknet(blocks=101, model_name="sknet101", **kwargs)
+
+
+def sknet152(**kwargs):
+    return get_sknet(blocks=152, model_name="sknet152", **kwargs)

@@ -68,6 +68,8 @@ P1R_DECLARE(64, 256)
 P1R_DECLARE(32, 512)
 P1R_DECLARE(32, 256)
 
+enum TileCfg { TILE_C32 = 0, TILE_C64 = 1, TILE_C128 = 2, TILE_C256 = 3, TILE_C64S = 4, TILE_C128S = 5, TILE_COUNT = 6 };
+
 struct pcv_ctx {
     int device = 0;
     std::string err;
@@ -76,6 +78,7 @@ struct pcv_ctx {
     int force_tile = -1;        // tuning only: force the implicit-GEMM tile (0..3) where legal
     int use_wstat = 1;          // weight-stationary persistent mode for single-K-step layers
     int use_mbr = 1;            // stride-1 fused inverted-residual units with Cin <= 32 run the register-resident kernel (mbr.hpp); 0: mbw.hpp / mbconv.hpp
+    int use_mbr_xl = 1;         // mbr.hpp instantiations that stage x through LDS; 0: never (A/B)
     int use_mbw = 1;            // fused inverted-residual units with Cin <= 32 run the wave-private kernel (mbw.hpp; 8 / 16: force that pixel-block width); 0: mbconv.hpp
     int use_gconvr = 1;         // grouped 3x3 stride 2 / 32 channels per group on the row-tile kernel (gconv3x3r.hpp); 0 = generic implicit GEMM
     int use_d1x1 = -1;          // K-heavy 1x1 layers on d3q_kernel's 1x1 mode: -1 = pick_d1x1, 0 = never, n > 0 = force shape n - 1 where eligible
@@ -99,6 +102,14 @@ struct pcv_ctx {
     int persist_max_nk = 4;     // auto: persistent when a tile has at most this many K-steps (PCV_AMD_PERSIST_NK)
     uint32_t* ovf = nullptr;    // device word: how many threads have rounded a value beyond fp16's range so far (F16Guard, pcv_common.hpp);
                                 // monotonic, never reset - pcv_fp16_guard_begin / _end compare two readings of it in stream order
+    // Resident blocks per CU of the persistent kernels ON THIS DEVICE (enable_kernels: the occupancy query, floor 1). These kernels use
+    // < 80 SGPRs, where the query is exact (MI355X_MICROARCH.md). Where one slot serves both 16-bit types it holds the fp16 instance's figure.
+    int igemm_bpc[3][2][TILE_COUNT][3] = {};     // [dt][variant: 0 regular, 1 ragged/f32-out][tile][khw slot]
+    int gconv_bpc[3] = {2, 2, 2};                // [gconv_slot(W)]
+    int stem_bpc[2] = {1, 1};                    // [bf16, fp16]: the plain 64-row form's, used by every form
+    int pair_bpc[2] = {1, 1};                    // [PB == 4, PB == 2]; the gated form launches with [1]
+    int pair_idc_bpc = 1;
+    int wpair_bpc[4] = {1, 1, 1, 1};             // [wpair_cfg]: the ungated form's, used by both
 };
 
 static thread_local std::string g_create_err;
@@ -135,6 +146,31 @@ static inline long long block_slots(const pcv_ctx* ctx, int per_cu) {
 static inline int esize(int dt) { return dt == PCV_F32 ? 4 : 2; }
 static inline bool dtype_ok(int dt) { return dt == PCV_F32 || dt == PCV_BF16 || dt == PCV_F16; }
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// the 2 GiB that one launch's buffer descriptors address
+static inline bool in_window(unsigned long long bytes) { return bytes < 0x80000000ull; }
+static int too_large(pcv_ctx* ctx, const char* fn, const char* what) {
+    return fail(ctx, PCV_ERR_TOO_LARGE, std::string(fn) + ": " + what + " exceeds the 2 GiB window of one launch; split the batch");
+}
+static const char* const kTensorTooLarge = "tensor exceeds the 2 GiB window";
+
+// One launchable kernel: entry point, block size, dynamic LDS bytes (the limit enable_kernels raises and the size launch() passes come
+// from this one field) and, where the family has tile shapes, output channels x pixels of a tile. Each family below has one table or
+// function that yields it from the selection parameters; enable_kernels walks the same.
+struct Kernel { const void* fn; int threads, lds, BM, BP; };
+template <class F> static Kernel kernel_of(F* fn, int threads, int lds, int BM = 0, int BP = 0) {
+    return Kernel{reinterpret_cast<const void*>(fn), threads, lds, BM, BP};
+}
+template <class Params> static int launch(pcv_ctx* ctx, const Kernel& k, unsigned grid, hipStream_t stream, Params& q) {
+    void* args[] = {&q};
+    HIP_TRY(ctx, hipLaunchKernel(k.fn, dim3(grid), dim3((unsigned)k.threads), args, (size_t)k.lds, stream));
+    return PCV_OK;
+}
+// resident blocks of `k` per CU of the current device (these kernels use < 80 SGPRs, where the query is exact - MI355X_MICROARCH.md)
+static int blocks_per_cu(pcv_ctx* ctx, const Kernel& k, int* nb) {
+    HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(nb, k.fn, k.threads, k.lds));
+    if (*nb < 1) *nb = 1;
+    return PCV_OK;
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // Convolution plan: everything that depends on the descriptor but not on the data pointers.
@@ -164,7 +200,7 @@ struct ConvPlan {
 };
 
 // A descriptor built by a binding that mirrors another layout of pcv_conv_desc (a stale ctypes stub) is refused, not read.
-static const char* kStaleDesc = "pcv_conv_desc.struct_size does not match this library (stale binding: compare pcv_conv_desc_size() / PCV_ABI_VERSION)";
+static const char* const kStaleDesc = "pcv_conv_desc.struct_size does not match this library (stale binding: compare pcv_conv_desc_size() / PCV_ABI_VERSION)";
 static inline bool desc_stale(const pcv_conv_desc& d) { return d.struct_size != (int32_t)sizeof(pcv_conv_desc); }
 
 static const char* plan_conv(const pcv_conv_desc& d, ConvPlan& P, bool tables) {
@@ -332,7 +368,6 @@ static const char* plan_conv(const pcv_conv_desc& d, ConvPlan& P, bool tables) {
 // ---------------------------------------------------------------------------------------------------------
 // Kernel table
 // ---------------------------------------------------------------------------------------------------------
-enum TileCfg { TILE_C32 = 0, TILE_C64 = 1, TILE_C128 = 2, TILE_C256 = 3, TILE_C64S = 4, TILE_C128S = 5, TILE_COUNT = 6 };
 struct TileInfo { int BM, BP, threads, lds; };
 static const TileInfo kTiles[TILE_COUNT] = {
     {32, 256, 256, 2 * (32 + 256) * 128},
@@ -362,7 +397,7 @@ template <int DT> static igemm_fn igemm_for_taps(int tile, int khw) {
 }
 // Non-ragged kernels store in the activation dtype; the ragged / fp32-output variants exist only on the 128x128 tile
 // (classifier logits, odd channel counts) with descriptor-driven taps.
-static igemm_fn pick_igemm(int dt, int ot, bool ragged, int tile, int khw) {
+static igemm_fn igemm_fn_for(int dt, int ot, bool ragged, int tile, int khw) {
     if (!ragged && ot == dt) {
         if (dt == PCV_BF16) return igemm_for_taps<PCV_BF16>(tile, khw);
         if (dt == PCV_F16) return igemm_for_taps<PCV_F16>(tile, khw);
@@ -379,54 +414,30 @@ static igemm_fn pick_igemm(int dt, int ot, bool ragged, int tile, int khw) {
     return nullptr;
 }
 
-// Every instantiation gets its dynamic-LDS limit raised once; the resident blocks per CU (for persistent grid sizing)
-// come from the occupancy query (these kernels use < 80 SGPRs, where the query is exact - MI355X_MICROARCH.md).
-static int g_blocks_per_cu[3][2][TILE_COUNT][3];     // [dt][variant: 0 regular, 1 ragged/f32-out][tile][khw slot]
-static inline int khw_slot(int khw) { return khw == 1 ? 1 : (khw == 9 ? 2 : 0); }
-
-static int enable_big_lds(pcv_ctx* ctx) {
-    static const int khws[3] = {0, 1, 9};
-    for (int dt = 0; dt < 3; ++dt)
-        for (int tile = 0; tile < TILE_COUNT; ++tile)
-            for (int ks = 0; ks < 3; ++ks)
-                for (int variant = 0; variant < 3; ++variant) {
-                    if (variant != 0 && ks != 0) continue;
-                    igemm_fn f = variant == 0 ? pick_igemm(dt, dt, false, tile, khws[ks])
-                               : variant == 1 ? pick_igemm(dt, PCV_F32, true, tile, 0)
-                                              : pick_igemm(dt, dt, true, tile, 0);
-                    if (f == nullptr) continue;
-                    HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(f),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, kTiles[tile].lds));
-                    int nb = 0;
-                    HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(f),
-                                                                              kTiles[tile].threads, kTiles[tile].lds));
-                    if (nb < 1) nb = 1;
-                    if (std::getenv("PCV_AMD_DEBUG"))
-                        std::fprintf(stderr, "[pcv] igemm dt=%d tile=%d khw=%d variant=%d: %d blocks/CU\n", dt, tile, khws[ks], variant, nb);
-                    if (variant == 0) g_blocks_per_cu[dt][0][tile][ks] = nb;
-                    else g_blocks_per_cu[dt][1][tile][0] = nb;
-                }
-    return PCV_OK;
+static Kernel igemm_kernel(int dt, int ot, bool ragged, int tile, int khw) {     // .fn == nullptr: no such instantiation
+    const TileInfo& T = kTiles[tile];
+    return kernel_of(igemm_fn_for(dt, ot, ragged, tile, khw), T.threads, T.lds, T.BM, T.BP);
 }
+static inline int khw_slot(int khw) { return khw == 1 ? 1 : (khw == 9 ? 2 : 0); }      // pcv_ctx::igemm_bpc
 
 // ---------------------------------------------------------------------------------------------------------
-typedef void (*gconv_fn)(const GConvParams);
-struct GConvLaunch { gconv_fn fn; int lds; };
-static GConvLaunch pick_gconv(int dt, int W) {
+static inline int gconv_slot(int W) { return W + 1 <= 16 ? 0 : (W + 1 <= 32 ? 1 : 2); }     // row width of the instantiation: 16 / 32 / 64
+static Kernel gconv_kernel(int dt, int slot) {
     const bool bf = dt == PCV_BF16;
-    if (W + 1 <= 16) return GConvLaunch{bf ? gconv3x3_kernel<PCV_BF16, 16> : gconv3x3_kernel<PCV_F16, 16>, GConvCfg<16>::LDS};
-    if (W + 1 <= 32) return GConvLaunch{bf ? gconv3x3_kernel<PCV_BF16, 32> : gconv3x3_kernel<PCV_F16, 32>, GConvCfg<32>::LDS};
-    return GConvLaunch{bf ? gconv3x3_kernel<PCV_BF16, 64> : gconv3x3_kernel<PCV_F16, 64>, GConvCfg<64>::LDS};
+    if (slot == 0) return kernel_of(bf ? gconv3x3_kernel<PCV_BF16, 16> : gconv3x3_kernel<PCV_F16, 16>, 256, GConvCfg<16>::LDS);
+    if (slot == 1) return kernel_of(bf ? gconv3x3_kernel<PCV_BF16, 32> : gconv3x3_kernel<PCV_F16, 32>, 256, GConvCfg<32>::LDS);
+    return kernel_of(bf ? gconv3x3_kernel<PCV_BF16, 64> : gconv3x3_kernel<PCV_F16, 64>, 256, GConvCfg<64>::LDS);
 }
 // ---- row-tile grouped kernel (gconv3x3r.hpp): R whole output rows per tile, R Wo <= 64, window rows a multiple of 32 ----------
-typedef void (*gconvr_fn)(const GConvRParams);
-static gconvr_fn pick_gconvr(int dt, int stride, int kt) {
+static const int kGconvRMaxLds = 160 * 1024;
+// `lds`: what the launch's row plan needs (2 x window rows x 128 bytes); the default is the limit every instantiation is enabled for
+static Kernel gconvr_kernel(int dt, int stride, int kt, int lds = kGconvRMaxLds) {
     const bool bf = dt == PCV_BF16;
     if (stride == 2) {
-        if (kt == 9) return bf ? gconv3x3r_kernel<PCV_BF16, 2, 9> : gconv3x3r_kernel<PCV_F16, 2, 9>;
-        return bf ? gconv3x3r_kernel<PCV_BF16, 2, 5> : gconv3x3r_kernel<PCV_F16, 2, 5>;
+        if (kt == 9) return kernel_of(bf ? gconv3x3r_kernel<PCV_BF16, 2, 9> : gconv3x3r_kernel<PCV_F16, 2, 9>, 256, lds);
+        return kernel_of(bf ? gconv3x3r_kernel<PCV_BF16, 2, 5> : gconv3x3r_kernel<PCV_F16, 2, 5>, 256, lds);
     }
-    return bf ? gconv3x3r_kernel<PCV_BF16, 1, 9> : gconv3x3r_kernel<PCV_F16, 1, 9>;   // stride 1, <= 16 channels per group: gconv3x3.hpp
+    return kernel_of(bf ? gconv3x3r_kernel<PCV_BF16, 1, 9> : gconv3x3r_kernel<PCV_F16, 1, 9>, 256, lds);   // stride 1, <= 16 channels per group: gconv3x3.hpp
 }
 struct GConvRPlan { int R, XH, xl, win; };
 static bool plan_gconvr(int stride, int H, int W, int Ho, int Wo, GConvRPlan& g) {
@@ -437,93 +448,55 @@ static bool plan_gconvr(int stride, int H, int W, int Ho, int Wo, GConvRPlan& g)
         const int XH = stride == 2 ? ((win + 1) / 2 + 7) / 8 * 8 : 0;
         const int rows = ((stride == 2 ? 2 * XH : win) + 31) / 32 * 32;
         const int lds = 2 * rows * 128;
-        if (lds * 2 <= 160 * 1024 || (R == 1 && lds <= 160 * 1024)) {  // two blocks per CU; a wide map may take a whole CU's LDS
+        if (lds * 2 <= kGconvRMaxLds || (R == 1 && lds <= kGconvRMaxLds)) {  // two blocks per CU; a wide map may take a whole CU's LDS
             g.R = R; g.XH = XH; g.xl = rows / 32; g.win = win;
             return true;
         }
     }
     return false;
 }
-static int enable_gconvr(pcv_ctx* ctx) {
-    for (int dt = PCV_BF16; dt <= PCV_F16; ++dt)
-        for (int s = 1; s <= 2; ++s)
-            for (int kt = 5; kt <= 9; kt += 4)
-                HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(pick_gconvr(dt, s, kt)),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    return PCV_OK;
-}
-static int g_gconv_blocks_per_cu[3] = {2, 2, 2};
-static int enable_gconv(pcv_ctx* ctx) {
-    const int widths[3] = {15, 31, 63};
-    for (int i = 0; i < 3; ++i)
-        for (int dt = PCV_BF16; dt <= PCV_F16; ++dt) {
-            const GConvLaunch L = pick_gconv(dt, widths[i]);
-            HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(L.fn), hipFuncAttributeMaxDynamicSharedMemorySize, L.lds));
-            int nb = 0;
-            HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(L.fn), 256, L.lds));
-            g_gconv_blocks_per_cu[i] = nb < 1 ? 1 : nb;
-        }
-    return PCV_OK;
-}
 // ---- 8-wave dense 3x3 kernel (d3q_conv.hpp) -----------------------------------------------------------------------------
-struct D3Shape { int BM, BP, lds; const void* fn[2]; };       // fn[0] bf16, fn[1] fp16
-#define D3Q_ROW(DT, WC, WP, CBW, PBW, KS)                                                                    \
-    {D3Cfg<WC, WP, CBW, PBW, KS>::BM, D3Cfg<WC, WP, CBW, PBW, KS>::BP, D3Cfg<WC, WP, CBW, PBW, KS>::LDS,     \
-     {reinterpret_cast<const void*>(d3q_kernel<PCV_BF16, WC, WP, CBW, PBW, KS>),                             \
-      reinterpret_cast<const void*>(d3q_kernel<PCV_F16, WC, WP, CBW, PBW, KS>)}},
-static const D3Shape kD3[] = {D3Q_SHAPES(D3Q_ROW, 0)};
+// The kernels that share D3Params (launch_d3): one row per tile shape, [0] bf16, [1] fp16
+template <class Cfg, class F> static Kernel tile_kernel(F* fn, int threads) { return kernel_of(fn, threads, Cfg::LDS, Cfg::BM, Cfg::BP); }
+#define D3Q_ROW(DT, WC, WP, CBW, PBW, KS)                                                                   \
+    {tile_kernel<D3Cfg<WC, WP, CBW, PBW, KS>>(d3q_kernel<PCV_BF16, WC, WP, CBW, PBW, KS>, 768),             \
+     tile_kernel<D3Cfg<WC, WP, CBW, PBW, KS>>(d3q_kernel<PCV_F16, WC, WP, CBW, PBW, KS>, 768)},
+static const Kernel kD3[][2] = {D3Q_SHAPES(D3Q_ROW, 0)};
 static const int kD3Count = (int)(sizeof(kD3) / sizeof(kD3[0]));
 // the same kernel in its 1x1 mode (K-heavy pointwise layers)
-#define D3Q1_ROW(DT, WC, WP, CBW, PBW, KS)                                                                                     \
-    {D3Cfg<WC, WP, CBW, PBW, KS, true>::BM, D3Cfg<WC, WP, CBW, PBW, KS, true>::BP, D3Cfg<WC, WP, CBW, PBW, KS, true>::LDS,      \
-     {reinterpret_cast<const void*>(d3q_kernel<PCV_BF16, WC, WP, CBW, PBW, KS, true>),                                        \
-      reinterpret_cast<const void*>(d3q_kernel<PCV_F16, WC, WP, CBW, PBW, KS, true>)}},
-static const D3Shape kD1[] = {D3Q1_SHAPES(D3Q1_ROW, 0)};
+#define D3Q1_ROW(DT, WC, WP, CBW, PBW, KS)                                                                  \
+    {tile_kernel<D3Cfg<WC, WP, CBW, PBW, KS, true>>(d3q_kernel<PCV_BF16, WC, WP, CBW, PBW, KS, true>, 768), \
+     tile_kernel<D3Cfg<WC, WP, CBW, PBW, KS, true>>(d3q_kernel<PCV_F16, WC, WP, CBW, PBW, KS, true>, 768)},
+static const Kernel kD1[][2] = {D3Q1_SHAPES(D3Q1_ROW, 0)};
 static const int kD1Count = (int)(sizeof(kD1) / sizeof(kD1[0]));
 // the large-tile kernel (d3w_conv.hpp): eight self-loading waves, 512 threads
-#define D3W_ROW(DT, WC, WP, CBW, PBW, KS, NSA)                                                                                   \
-    {D3WCfg<WC, WP, CBW, PBW, KS, NSA>::BM, D3WCfg<WC, WP, CBW, PBW, KS, NSA>::BP, D3WCfg<WC, WP, CBW, PBW, KS, NSA>::LDS,       \
-     {reinterpret_cast<const void*>(d3w_kernel<PCV_BF16, WC, WP, CBW, PBW, KS, NSA>),                                           \
-      reinterpret_cast<const void*>(d3w_kernel<PCV_F16, WC, WP, CBW, PBW, KS, NSA>)}},
-#define D3WT_ROW(DT, WC, WP, CBW, PBW, KS, NSA, TRIM)                                                                                               \
-    {D3WCfg<WC, WP, CBW, PBW, KS, NSA, TRIM>::BM, D3WCfg<WC, WP, CBW, PBW, KS, NSA, TRIM>::BP, D3WCfg<WC, WP, CBW, PBW, KS, NSA, TRIM>::LDS,       \
-     {reinterpret_cast<const void*>(d3w_kernel<PCV_BF16, WC, WP, CBW, PBW, KS, NSA, TRIM>),                                                       \
-      reinterpret_cast<const void*>(d3w_kernel<PCV_F16, WC, WP, CBW, PBW, KS, NSA, TRIM>)}},
-static const D3Shape kD3W[] = {D3W_SHAPES(D3W_ROW, 0) D3WT_SHAPES(D3WT_ROW, 0)};
+#define D3W_ROW(DT, WC, WP, CBW, PBW, KS, NSA)                                                              \
+    {tile_kernel<D3WCfg<WC, WP, CBW, PBW, KS, NSA>>(d3w_kernel<PCV_BF16, WC, WP, CBW, PBW, KS, NSA>, 512),  \
+     tile_kernel<D3WCfg<WC, WP, CBW, PBW, KS, NSA>>(d3w_kernel<PCV_F16, WC, WP, CBW, PBW, KS, NSA>, 512)},
+#define D3WT_ROW(DT, WC, WP, CBW, PBW, KS, NSA, TRIM)                                                                   \
+    {tile_kernel<D3WCfg<WC, WP, CBW, PBW, KS, NSA, TRIM>>(d3w_kernel<PCV_BF16, WC, WP, CBW, PBW, KS, NSA, TRIM>, 512),  \
+     tile_kernel<D3WCfg<WC, WP, CBW, PBW, KS, NSA, TRIM>>(d3w_kernel<PCV_F16, WC, WP, CBW, PBW, KS, NSA, TRIM>, 512)},
+static const Kernel kD3W[][2] = {D3W_SHAPES(D3W_ROW, 0) D3WT_SHAPES(D3WT_ROW, 0)};
 static const int kD3WCount = (int)(sizeof(kD3W) / sizeof(kD3W[0]));
-static const void* kD3C[2] = {reinterpret_cast<const void*>(d3c_kernel<PCV_BF16>), reinterpret_cast<const void*>(d3c_kernel<PCV_F16>)};
-static const void* kD3I[2][2] = {{reinterpret_cast<const void*>(d3i_kernel<PCV_BF16, 256>), reinterpret_cast<const void*>(d3i_kernel<PCV_F16, 256>)},
-                                 {reinterpret_cast<const void*>(d3i_kernel<PCV_BF16, 512>), reinterpret_cast<const void*>(d3i_kernel<PCV_F16, 512>)}};
-static const void* kD1I[2][2] = {{reinterpret_cast<const void*>(d1i_kernel<PCV_BF16, 1024>), reinterpret_cast<const void*>(d1i_kernel<PCV_F16, 1024>)},
-                                 {reinterpret_cast<const void*>(d1i_kernel<PCV_BF16, 2048>), reinterpret_cast<const void*>(d1i_kernel<PCV_F16, 2048>)}};
-static const void* kD3K[2] = {reinterpret_cast<const void*>(d3k_kernel<PCV_BF16>), reinterpret_cast<const void*>(d3k_kernel<PCV_F16>)};
+// the register-weight kernels of ResNet stages 1 / 2 (256 threads, tiles = ROWS output rows of one image)
+static const Kernel kD3C[1][2] = {{tile_kernel<D3CCfg>(d3c_kernel<PCV_BF16>, 256), tile_kernel<D3CCfg>(d3c_kernel<PCV_F16>, 256)}};
+static const Kernel kD3K[1][2] = {{tile_kernel<D3KCfg>(d3k_kernel<PCV_BF16>, 256), tile_kernel<D3KCfg>(d3k_kernel<PCV_F16>, 256)}};
+// d3i_conv.hpp: [0] 256, [1] 512 input channels; one block per (image(s), 256-channel tile), no pixel tiling
+#define D3I_ROW(CIN)                                                                              \
+    {kernel_of(d3i_kernel<PCV_BF16, CIN>, D3ICfg::THREADS, D3ICfgT<CIN>::LDS, D3ICfg::BM),        \
+     kernel_of(d3i_kernel<PCV_F16, CIN>, D3ICfg::THREADS, D3ICfgT<CIN>::LDS, D3ICfg::BM)}
+static const Kernel kD3I[2][2] = {D3I_ROW(256), D3I_ROW(512)};
+// d1i_conv.hpp: [0] 1024, [1] 2048 input channels; the tile (256 channels x 208 pixels) and the LDS ring are those of the 1024 form for both
+static const Kernel kD1I[2][2] = {
+    {tile_kernel<D1ICfgT<1024>>(d1i_kernel<PCV_BF16, 1024>, 256), tile_kernel<D1ICfgT<1024>>(d1i_kernel<PCV_F16, 1024>, 256)},
+    {tile_kernel<D1ICfgT<1024>>(d1i_kernel<PCV_BF16, 2048>, 256), tile_kernel<D1ICfgT<1024>>(d1i_kernel<PCV_F16, 2048>, 256)}};
 // p1r_conv.hpp: [0] 256 input channels (8 waves x 64 channels), [1] 512 input channels (8 waves x 32 channels), [2] 256 input channels with
 // 32 channels per wave (a skip tensor, or fewer than 384 output channels)
-#define P1R_ROW(CW, CIN)                                                                   \
-    {P1RCfg<CW, CIN>::BM, P1RCfg<CW, CIN>::BP, P1RCfg<CW, CIN>::LDS,                       \
-     {reinterpret_cast<const void*>(p1r_kernel<PCV_BF16, CW, CIN>), reinterpret_cast<const void*>(p1r_kernel<PCV_F16, CW, CIN>)}}
-static const D3Shape kP1R[3] = {P1R_ROW(64, 256), P1R_ROW(32, 512), P1R_ROW(32, 256)};
-static int enable_d3x3(pcv_ctx* ctx) {
-    for (int i = 0; i < 3; ++i)
-        for (int t = 0; t < 2; ++t) HIP_TRY(ctx, hipFuncSetAttribute(kP1R[i].fn[t], hipFuncAttributeMaxDynamicSharedMemorySize, kP1R[i].lds));
-    for (int t = 0; t < 2; ++t) HIP_TRY(ctx, hipFuncSetAttribute(kD3C[t], hipFuncAttributeMaxDynamicSharedMemorySize, D3CCfg::LDS));
-    for (int t = 0; t < 2; ++t) HIP_TRY(ctx, hipFuncSetAttribute(kD3K[t], hipFuncAttributeMaxDynamicSharedMemorySize, D3KCfg::LDS));
-    for (int i = 0; i < 2; ++i)
-        for (int t = 0; t < 2; ++t) HIP_TRY(ctx, hipFuncSetAttribute(kD1I[i][t], hipFuncAttributeMaxDynamicSharedMemorySize, D1ICfgT<1024>::LDS));
-    for (int t = 0; t < 2; ++t) HIP_TRY(ctx, hipFuncSetAttribute(kD3I[0][t], hipFuncAttributeMaxDynamicSharedMemorySize, D3ICfgT<256>::LDS));
-    for (int t = 0; t < 2; ++t) HIP_TRY(ctx, hipFuncSetAttribute(kD3I[1][t], hipFuncAttributeMaxDynamicSharedMemorySize, D3ICfgT<512>::LDS));
-    for (int i = 0; i < kD3WCount; ++i)
-        for (int t = 0; t < 2; ++t)
-            HIP_TRY(ctx, hipFuncSetAttribute(kD3W[i].fn[t], hipFuncAttributeMaxDynamicSharedMemorySize, kD3W[i].lds));
-
-    for (int i = 0; i < kD3Count; ++i)
-        for (int t = 0; t < 2; ++t)
-            HIP_TRY(ctx, hipFuncSetAttribute(kD3[i].fn[t], hipFuncAttributeMaxDynamicSharedMemorySize, kD3[i].lds));
-    for (int i = 0; i < kD1Count; ++i)
-        for (int t = 0; t < 2; ++t)
-            HIP_TRY(ctx, hipFuncSetAttribute(kD1[i].fn[t], hipFuncAttributeMaxDynamicSharedMemorySize, kD1[i].lds));
-    return PCV_OK;
-}
+#define P1R_ROW(CW, CIN) \
+    {tile_kernel<P1RCfg<CW, CIN>>(p1r_kernel<PCV_BF16, CW, CIN>, 512), tile_kernel<P1RCfg<CW, CIN>>(p1r_kernel<PCV_F16, CW, CIN>, 512)}
+static const Kernel kP1R[3][2] = {P1R_ROW(64, 256), P1R_ROW(32, 512), P1R_ROW(32, 256)};
+static const struct { const Kernel (*rows)[2]; int n; } kD3Tables[] = {{kD3, kD3Count}, {kD1, kD1Count}, {kD3W, kD3WCount}, {kD3C, 1},
+                                                                       {kD3K, 1},       {kD3I, 2},       {kD1I, 2},         {kP1R, 3}};
 // 1x1 mode: which pointwise layers go to the 8 + 4-wave kernel: K >= 256 and >= 128 output channels (the short-K layers keep the
 // 4-wave kernel; where a fused pair applies the caller takes that first). Measured at batch 256 (us, generic -> this kernel):
 // 512->256 @28x28 106 -> 90, 512->1024 + skip @14x14 93 -> 85, 256->1024 + skip 69 -> 60, 1024->512 74 -> 72, 2048->512 @7x7 43 -> 39;
@@ -531,7 +504,7 @@ static int enable_d3x3(pcv_ctx* ctx) {
 static int pick_d1x1(long long M, int Cout, int Cin, long long slots) {
     if (Cin < 256 || Cout < 128) return -1;
     const int shape = Cout % 256 == 0 ? 1 : 0;
-    const long long tiles = (long long)((Cout + kD1[shape].BM - 1) / kD1[shape].BM) * ((M + kD1[shape].BP - 1) / kD1[shape].BP);
+    const long long tiles = (long long)((Cout + kD1[shape][0].BM - 1) / kD1[shape][0].BM) * ((M + kD1[shape][0].BP - 1) / kD1[shape][0].BP);
     return tiles * 2 >= slots ? shape : -1;                      // too few tiles to fill the chip with one block per CU: 4-wave kernel
 }
 // Tile shape for M pixels x Cout channels on `slots` CUs (one block each). With the activation tile staged once per filter row
@@ -543,7 +516,7 @@ static int pick_d1x1(long long M, int Cout, int Cin, long long slots) {
 static int pick_d3x3(long long M, int Cout, int nk, long long slots) {
     (void)nk;
     const int wide = Cout <= 64 ? 2 : 1, narrow = Cout <= 64 ? 5 : 4;          // d3q_inst.hpp order
-    auto tiles = [&](int i) { return ((Cout + kD3[i].BM - 1) / kD3[i].BM) * ((M + kD3[i].BP - 1) / kD3[i].BP); };
+    auto tiles = [&](int i) { return ((Cout + kD3[i][0].BM - 1) / kD3[i][0].BM) * ((M + kD3[i][0].BP - 1) / kD3[i][0].BP); };
     // (512 channels at 7x7, batch 256: 224 tiles either way - 256 x 112 measured 66.9 / 70.9 us (plain / + skip) against 68.5 / 72.2 for 128 x 224)
     if (Cout % 256 == 0 && tiles(0) * 2 >= slots) return 0;
     if (tiles(wide) * 2 >= slots) return wide;
@@ -557,56 +530,41 @@ static int pick_d3x3(long long M, int Cout, int nk, long long slots) {
 static int pick_d3w(long long M, int Cout, long long slots) {
     const int shape = Cout % 256 == 0 ? 1 : (Cout % 128 == 0 ? 2 : -1);
     if (shape < 0) return -1;
-    const long long tiles = (long long)(Cout / kD3W[shape].BM) * ((M + kD3W[shape].BP - 1) / kD3W[shape].BP);
+    const long long tiles = (long long)(Cout / kD3W[shape][0].BM) * ((M + kD3W[shape][0].BP - 1) / kD3W[shape][0].BP);
     return tiles * 4 >= slots * 3 ? shape : -1;
 }
 
 // ---- stem kernel ------------------------------------------------------------------------------------------------------
 static const int kStemLds = 7 * 64 * 64 + 2 * 768 * 16 + 3 * 2 * 64 * 16;     // weights + 2 patches + the pooled variant's row hand-down
-static int g_stem_blocks_per_cu[2];
-static int enable_stem(pcv_ctx* ctx) {
-    const void* fns[2] = {reinterpret_cast<const void*>(stem_conv_kernel<PCV_BF16, false>),
-                          reinterpret_cast<const void*>(stem_conv_kernel<PCV_F16, false>)};
-    const void* pooled[2] = {reinterpret_cast<const void*>(stem_conv_kernel<PCV_BF16, true>),
-                             reinterpret_cast<const void*>(stem_conv_kernel<PCV_F16, true>)};
-    for (int i = 0; i < 2; ++i) HIP_TRY(ctx, hipFuncSetAttribute(pooled[i], hipFuncAttributeMaxDynamicSharedMemorySize, kStemLds));
-    const void* from_nchw[4] = {reinterpret_cast<const void*>(stem_conv_kernel<PCV_BF16, false, true>),
-                                reinterpret_cast<const void*>(stem_conv_kernel<PCV_F16, false, true>),
-                                reinterpret_cast<const void*>(stem_conv_kernel<PCV_BF16, true, true>),
-                                reinterpret_cast<const void*>(stem_conv_kernel<PCV_F16, true, true>)};
-    for (int i = 0; i < 4; ++i)
-        HIP_TRY(ctx, hipFuncSetAttribute(from_nchw[i], hipFuncAttributeMaxDynamicSharedMemorySize, kStemLds + kStemStageBytes));
-    // the 32-channel form (stems with at most 32 output channels, no fused pool)
-    const void* narrow[4] = {reinterpret_cast<const void*>(stem_conv_kernel<PCV_BF16, false, false, 2>),
-                             reinterpret_cast<const void*>(stem_conv_kernel<PCV_F16, false, false, 2>),
-                             reinterpret_cast<const void*>(stem_conv_kernel<PCV_BF16, false, true, 2>),
-                             reinterpret_cast<const void*>(stem_conv_kernel<PCV_F16, false, true, 2>)};
-    for (int i = 0; i < 4; ++i)
-        HIP_TRY(ctx, hipFuncSetAttribute(narrow[i], hipFuncAttributeMaxDynamicSharedMemorySize, kStemLds + (i >= 2 ? kStemStageBytes : 0)));
-    for (int i = 0; i < 2; ++i) {
-        HIP_TRY(ctx, hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, kStemLds));
-        int nb = 0;
-        HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fns[i], 256, kStemLds));
-        g_stem_blocks_per_cu[i] = nb < 1 ? 1 : nb;
-    }
-    return PCV_OK;
-}
+enum StemForm { STEM_PLAIN = 0, STEM_POOLED = 1, STEM_NARROW = 2 };      // 64 channel rows; + fused max-pool; 32 channel rows (no pool)
+// [bf16, fp16][x: padded NHWC4, fp32 NCHW (staged through kStemStageBytes more LDS)][StemForm]
+#define STEM_ROWS(DT)                                                                                                          \
+    {{kernel_of(stem_conv_kernel<DT, false>, 256, kStemLds), kernel_of(stem_conv_kernel<DT, true>, 256, kStemLds),             \
+      kernel_of(stem_conv_kernel<DT, false, false, 2>, 256, kStemLds)},                                                        \
+     {kernel_of(stem_conv_kernel<DT, false, true>, 256, kStemLds + kStemStageBytes),                                           \
+      kernel_of(stem_conv_kernel<DT, true, true>, 256, kStemLds + kStemStageBytes),                                            \
+      kernel_of(stem_conv_kernel<DT, false, true, 2>, 256, kStemLds + kStemStageBytes)}}
+static const Kernel kStem[2][2][3] = {STEM_ROWS(PCV_BF16), STEM_ROWS(PCV_F16)};
 
 static int pair_lds(int pb, bool idc = false) { return (idc ? 6 : 3) * 16 * pb * 64 * 2 + 16 * 1024 * pb + (idc ? 4096 : 0); }   // x (+ x0) ring + reduction buffer
-static int g_pair_idc_blocks_per_cu = 1;
-static int g_pair_blocks_per_cu[2] = {1, 1};                                        // [PB == 4, PB == 2]
-static int g_wpair_mask = 3;                                                        // bit 0: CM = 128, bit 1: CM = 256 (tuning)
-static int g_wpair_blocks_per_cu[4] = {1, 1, 1, 1};
+enum PairForm { PAIR_PB4 = 0, PAIR_PB2 = 1, PAIR_GATED = 2, PAIR_IDCONV = 3 };     // (gated and identity-convolution forms: PB == 2)
+#define PAIR_ROW(DT)                                                                                                          \
+    {kernel_of(pair1x1_kernel<DT, 4>, 256, pair_lds(4)), kernel_of(pair1x1_kernel<DT, 2>, 256, pair_lds(2)),                  \
+     kernel_of(pair1x1_kernel<DT, 2, false, true>, 256, pair_lds(2)), kernel_of(pair1x1_kernel<DT, 2, true>, 256, pair_lds(2, true))}
+static const Kernel kPair[2][4] = {PAIR_ROW(PCV_BF16), PAIR_ROW(PCV_F16)};      // [bf16, fp16][PairForm]
+// The two switches that stay process-wide: the context-free *_supported predicates of the ABI read them (pcv_set_tuning writes them
+// through any context, for every context).
+static int g_wpair_mask = 3;            // "wpair": bit 0: CM = 128, bit 1: CM = 256
+static int g_mbw_wide = 1;              // "mbw_wide": mbw.hpp's units with 65..96 projected channels (mbw_shape)
 // wide pair configurations: 0: 128 -> 512, 1: 256 -> 1024 (ResNet), 2: 128 -> 256, 3: 256 -> 512 (ResNeXt 32x4d)
-struct WPairLaunch { const void* fn; int threads, lds, tileP; bool gate_in_lds; };
+struct WPairLaunch { Kernel k; int tileP; bool gate_in_lds; };
 template <int CM, int C1> static WPairLaunch wpair_launch_for(int dt, bool gated) {
     typedef WPairCfg<CM, C1> G;
-    const void* fn;
-    if (gated) fn = dt == PCV_BF16 ? reinterpret_cast<const void*>(wpair1x1_kernel<PCV_BF16, CM, C1, true>)
-                                   : reinterpret_cast<const void*>(wpair1x1_kernel<PCV_F16, CM, C1, true>);
-    else fn = dt == PCV_BF16 ? reinterpret_cast<const void*>(wpair1x1_kernel<PCV_BF16, CM, C1, false>)
-                             : reinterpret_cast<const void*>(wpair1x1_kernel<PCV_F16, CM, C1, false>);
-    return WPairLaunch{fn, 64 * G::NW, gated ? G::LDS_GATED : G::LDS, G::P, gated && G::GATE_LDS};
+    const bool bf = dt == PCV_BF16;
+    const int lds = gated ? G::LDS_GATED : G::LDS;
+    const Kernel k = gated ? kernel_of(bf ? wpair1x1_kernel<PCV_BF16, CM, C1, true> : wpair1x1_kernel<PCV_F16, CM, C1, true>, 64 * G::NW, lds)
+                           : kernel_of(bf ? wpair1x1_kernel<PCV_BF16, CM, C1, false> : wpair1x1_kernel<PCV_F16, CM, C1, false>, 64 * G::NW, lds);
+    return WPairLaunch{k, G::P, gated && G::GATE_LDS};
 }
 static WPairLaunch wpair_launch(int cfg, int dt, bool gated = false) {
     switch (cfg) {
@@ -623,51 +581,17 @@ static int wpair_cfg(int cm, int c1) {
     if (cm == 256 && c1 == 512) return 3;
     return -1;
 }
-static int enable_pair(pcv_ctx* ctx) {
-    const void* fns[4] = {reinterpret_cast<const void*>(pair1x1_kernel<PCV_BF16, 4>),
-                          reinterpret_cast<const void*>(pair1x1_kernel<PCV_F16, 4>),
-                          reinterpret_cast<const void*>(pair1x1_kernel<PCV_BF16, 2>),
-                          reinterpret_cast<const void*>(pair1x1_kernel<PCV_F16, 2>)};
-    for (int i = 0; i < 4; ++i) {
-        const int lds = pair_lds(i < 2 ? 4 : 2);
-        HIP_TRY(ctx, hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        int nb = 0;
-        HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fns[i], 256, lds));
-        g_pair_blocks_per_cu[i / 2] = nb < 1 ? 1 : nb;
-    }
-    const void* gated[2] = {reinterpret_cast<const void*>(pair1x1_kernel<PCV_BF16, 2, false, true>),
-                            reinterpret_cast<const void*>(pair1x1_kernel<PCV_F16, 2, false, true>)};
-    for (int i = 0; i < 2; ++i) HIP_TRY(ctx, hipFuncSetAttribute(gated[i], hipFuncAttributeMaxDynamicSharedMemorySize, pair_lds(2)));
-    const void* idc[2] = {reinterpret_cast<const void*>(pair1x1_kernel<PCV_BF16, 2, true>),
-                          reinterpret_cast<const void*>(pair1x1_kernel<PCV_F16, 2, true>)};
-    for (int i = 0; i < 2; ++i) {
-        HIP_TRY(ctx, hipFuncSetAttribute(idc[i], hipFuncAttributeMaxDynamicSharedMemorySize, pair_lds(2, true)));
-        int nb = 0;
-        HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, idc[i], 256, pair_lds(2, true)));
-        g_pair_idc_blocks_per_cu = nb < 1 ? 1 : nb;
-    }
-    for (int cfg = 0; cfg < 4; ++cfg)
-        for (int dt = PCV_BF16; dt <= PCV_F16; ++dt) {
-            const WPairLaunch L = wpair_launch(cfg, dt);
-            HIP_TRY(ctx, hipFuncSetAttribute(L.fn, hipFuncAttributeMaxDynamicSharedMemorySize, L.lds));
-            HIP_TRY(ctx, hipFuncSetAttribute(wpair_launch(cfg, dt, true).fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             wpair_launch(cfg, dt, true).lds));
-            int nb = 0;
-            HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, L.fn, L.threads, L.lds));
-            g_wpair_blocks_per_cu[cfg] = nb < 1 ? 1 : nb;
-        }
-    return PCV_OK;
+// a 1x1 convolution with nothing but channels: stride 1, no padding, one group, dense x and y in the input's type
+static bool plain_1x1(const pcv_conv_desc& d) {
+    return d.kh == 1 && d.kw == 1 && d.stride_h == 1 && d.stride_w == 1 && d.pad_t == 0 && d.pad_l == 0 && d.pad_b == 0 &&
+           d.pad_r == 0 && d.groups == 1 && d.dil_h == 1 && d.dil_w == 1 && d.out_dtype == d.dtype &&
+           (d.x_cpitch == 0 || d.x_cpitch == d.Cin) && (d.x_wpitch == 0 || d.x_wpitch == d.W) &&
+           (d.y_cpitch == 0 || d.y_cpitch == d.Cout);
 }
 // Which (conv, next conv) pairs the fused kernel covers: 1x1/s1 64 -> 256 with residual, then 1x1/s1 256 -> 64, 16 bit.
 static const char* pair_unsupported(const pcv_conv_desc& a, const pcv_conv_desc& b) {
     if (desc_stale(a) || desc_stale(b)) return kStaleDesc;
-    auto plain1x1 = [](const pcv_conv_desc& d) {
-        return d.kh == 1 && d.kw == 1 && d.stride_h == 1 && d.stride_w == 1 && d.pad_t == 0 && d.pad_l == 0 && d.pad_b == 0 &&
-               d.pad_r == 0 && d.groups == 1 && d.dil_h == 1 && d.dil_w == 1 && d.out_dtype == d.dtype &&
-               (d.x_cpitch == 0 || d.x_cpitch == d.Cin) && (d.x_wpitch == 0 || d.x_wpitch == d.W) &&
-               (d.y_cpitch == 0 || d.y_cpitch == d.Cout);
-    };
-    if (!plain1x1(a) || !plain1x1(b)) return "both convolutions must be plain 1x1 stride 1";
+    if (!plain_1x1(a) || !plain_1x1(b)) return "both convolutions must be plain 1x1 stride 1";
     if (a.dtype != b.dtype || (a.dtype != PCV_BF16 && a.dtype != PCV_F16)) return "16-bit storage only";
     if (a.N != b.N || a.H != b.H || a.W != b.W || a.Cout != b.Cin) return "shapes do not chain";
     const bool narrow = a.Cin == 64 && a.Cout == 256 && b.Cout == 64;        // pair1x1.hpp: weights in registers
@@ -675,7 +599,7 @@ static const char* pair_unsupported(const pcv_conv_desc& a, const pcv_conv_desc&
                       wpair_cfg(a.Cin, a.Cout) >= 0 && b.Cout == a.Cin;   // wpair1x1.hpp: weights through an LDS ring
     if (!narrow && !wide) return "only 64 -> 256 -> 64, 128 -> 512|256 -> 128 and 256 -> 1024|512 -> 256 are instantiated";
     if (!a.has_residual || b.has_residual || b.post_act != PCV_ACT_NONE) return "first conv must carry the residual, second must not";
-    if ((long)a.N * a.H * a.W * a.Cout * 2 >= (1L << 31)) return "tensor exceeds the 2 GiB window";
+    if ((long)a.N * a.H * a.W * a.Cout * 2 >= (1L << 31)) return kTensorTooLarge;
     return nullptr;
 }
 
@@ -685,9 +609,12 @@ template <int DT, int RT> static mbconv_fn mbconv_for(int stride, bool expand) {
     if (stride == 1) return expand ? mbconv_kernel<DT, 1, true, RT> : mbconv_kernel<DT, 1, false, RT>;
     return expand ? mbconv_kernel<DT, 2, true, RT> : mbconv_kernel<DT, 2, false, RT>;
 }
-static mbconv_fn pick_mbconv(int dt, int stride, bool expand, int nrowt) {
-    if (dt == PCV_BF16) return nrowt <= 2 ? mbconv_for<PCV_BF16, 2>(stride, expand) : mbconv_for<PCV_BF16, 6>(stride, expand);
-    return nrowt <= 2 ? mbconv_for<PCV_F16, 2>(stride, expand) : mbconv_for<PCV_F16, 6>(stride, expand);
+// The three fused-unit kernels size their LDS per unit (mbconv_plan / mbw_lds_layout / mbr_entry_lds): the launch passes that size as
+// `lds`, the default is the limit every instantiation is enabled for.
+static const int kMbMaxLds = 150 * 1024, kMbwMaxLds = 160 * 1024;
+static Kernel mbconv_kernel(int dt, int stride, bool expand, int nrowt, int lds = kMbMaxLds) {
+    if (dt == PCV_BF16) return kernel_of(nrowt <= 2 ? mbconv_for<PCV_BF16, 2>(stride, expand) : mbconv_for<PCV_BF16, 6>(stride, expand), 256, lds);
+    return kernel_of(nrowt <= 2 ? mbconv_for<PCV_F16, 2>(stride, expand) : mbconv_for<PCV_F16, 6>(stride, expand), 256, lds);
 }
 // wave-private variant (mbw.hpp): Cin <= 32, Cout <= 64
 struct MbwEntry { int dt, s, nrt, act, tw, ka, rb; mbconv_fn fn; };
@@ -697,13 +624,13 @@ struct MbwEntry { int dt, s, nrt, act, tw, ka, rb; mbconv_fn fn; };
 static const MbwEntry kMbw[] = {MBW_SHAPES(MBW_ROW, PCV_BF16) MBW_SHAPES(MBW_ROW, PCV_F16) MBW2_SHAPES(MBW2_ROW, PCV_BF16)
                                 MBW2_SHAPES(MBW2_ROW, PCV_F16) MBW3_SHAPES(MBW3_ROW, PCV_BF16) MBW3_SHAPES(MBW3_ROW, PCV_F16)};
 // act: PCV_ACT_RELU / PCV_ACT_RELU6 when both inner activations are that one, anything else = the launch-time codes
-static mbconv_fn pick_mbw(int dt, int stride, int nrt, int act, int tw, int ka, int rb) {
+static const MbwEntry* pick_mbw(int dt, int stride, int nrt, int act, int tw, int ka, int rb) {
     if (act != PCV_ACT_RELU && act != PCV_ACT_RELU6) act = -1;
     for (const MbwEntry& e : kMbw)
-        if (e.dt == dt && e.s == stride && e.nrt == nrt && e.act == act && e.tw == tw && e.ka == ka && e.rb == rb) return e.fn;
+        if (e.dt == dt && e.s == stride && e.nrt == nrt && e.act == act && e.tw == tw && e.ka == ka && e.rb == rb) return &e;
     return nullptr;
 }
-static int g_mbr_xl = 1;     // pcv_set_tuning("mbr_xl", 0): never stage x through LDS (A/B)
+static Kernel mbw_kernel_of(const MbwEntry& e, int waves = 8, int lds = kMbwMaxLds) { return kernel_of(e.fn, 64 * waves, lds); }
 // register-resident variant (mbr.hpp): stride 1, Cin <= 32, Cout <= 64
 struct MbrEntry { int dt, nrt, act, ro, s, ka; bool afl; int waves; bool wel, xl; mbconv_fn fn; };
 #define MBR_ROW(DT, NRT, ACT, RO, S, KA, AFL, WV, WEL, XL) {DT, NRT, ACT, RO, S, KA, AFL, WV, WEL, XL, mbr_kernel<DT, NRT, ACT, RO, S, KA, AFL, WV, WEL, XL>},
@@ -712,23 +639,22 @@ static int mbr_entry_lds(const MbrEntry& e, int nChunks) {
     return mbr_lds_layout(e.nrt, nChunks, e.ka, e.afl, e.wel, e.xl ? nr : 0, e.waves).total;
 }
 static const MbrEntry kMbr[] = {MBR_SHAPES(MBR_ROW, PCV_BF16) MBR_SHAPES(MBR_ROW, PCV_F16)};
+static Kernel mbr_kernel_of(const MbrEntry& e, int lds = kMbwMaxLds) { return kernel_of(e.fn, 64 * e.waves, lds); }
 // the instantiation for a unit, when its tables fit the LDS
-static const MbrEntry* pick_mbr(int dt, int nrt, int act, int stride, int ka, int nChunks) {
+static const MbrEntry* pick_mbr(const pcv_ctx* ctx, int dt, int nrt, int act, int stride, int ka, int nChunks) {
     if (act != PCV_ACT_RELU && act != PCV_ACT_RELU6) return nullptr;          // launch-time activations: mbw.hpp / mbconv.hpp (mbr_inst.hpp)
     for (const MbrEntry& e : kMbr)
         if (e.dt == dt && e.nrt == nrt && e.act == act && e.s == stride && e.ka == ka &&
-            mbr_entry_lds(e, nChunks) <= 160 * 1024 && (!e.xl || g_mbr_xl))
+            mbr_entry_lds(e, nChunks) <= kMbwMaxLds && (!e.xl || ctx->use_mbr_xl))
             return &e;
     return nullptr;
 }
-static const int kMbwMaxLds = 160 * 1024;
 // waves per block (one block per CU): as many of 8 / 6 / 4 as the LDS holds beside the unit's weights; 0 = does not fit
 static int mbw_waves(int stride, int nrt, int nChunks, int tw, int ka, int rb) {
     for (int nw = 8; nw >= 4; nw -= 2)
         if (mbw_lds_layout(stride, nrt, nChunks, nw, tw, ka, rb).total <= kMbwMaxLds) return nw;
     return 0;
 }
-static const int kMbMaxLds = 150 * 1024;
 // LDS plan of one unit: prefetch the next tile's x (two buffers) when that still leaves room for two blocks per CU
 static MbLds mbconv_plan(int stride, bool expand, int ka, int nChunks, int nRowT, int* nbufX) {
     MbLds two = mb_lds_layout(stride, expand, ka, nChunks, nRowT, 2);
@@ -738,24 +664,73 @@ static MbLds mbconv_plan(int stride, bool expand, int ka, int nChunks, int nRowT
     *nbufX = 2;
     return two;
 }
-static int enable_mbconv(pcv_ctx* ctx) {
+
+// ---- once per context: every instantiation with dynamic LDS gets its limit raised on the context's device, and the persistent
+// kernels whose grid is a number of resident blocks get that number recorded in the context ---------------------------------------
+static int enable_kernel(pcv_ctx* ctx, const Kernel& k, int* bpc) {
+    HIP_TRY(ctx, hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds));
+    return bpc ? blocks_per_cu(ctx, k, bpc) : PCV_OK;
+}
+static int enable_kernels(pcv_ctx* ctx) {
+    int rc = PCV_OK;
+    auto on = [&](const Kernel& k, int* bpc = nullptr) {        // (.fn == nullptr: a combination that is not instantiated)
+        if (rc == PCV_OK && k.fn != nullptr) rc = enable_kernel(ctx, k, bpc);
+    };
+    auto report = [&](const Kernel& k, int dt, int tile, int khw, int variant) {
+        int nb = 0;
+        if (rc == PCV_OK && k.fn != nullptr && std::getenv("PCV_AMD_DEBUG") && blocks_per_cu(ctx, k, &nb) == PCV_OK)
+            std::fprintf(stderr, "[pcv] igemm dt=%d tile=%d khw=%d variant=%d: %d blocks/CU\n", dt, tile, khw, variant, nb);
+    };
+    static const int khws[3] = {0, 1, 9};
+    for (int dt = 0; dt < 3; ++dt)
+        for (int tile = 0; tile < TILE_COUNT; ++tile) {
+            for (int ks = 0; ks < 3; ++ks) {
+                const Kernel k = igemm_kernel(dt, dt, false, tile, khws[ks]);
+                on(k, &ctx->igemm_bpc[dt][0][tile][ks]);
+                report(k, dt, tile, khws[ks], 0);
+            }
+            // the two descriptor-driven variants (fp32 output; ragged in the input's type) share a slot: the second one's figure
+            const Kernel f32out = igemm_kernel(dt, PCV_F32, true, tile, 0), same = igemm_kernel(dt, dt, true, tile, 0);
+            on(f32out);
+            report(f32out, dt, tile, 0, 1);
+            on(same, &ctx->igemm_bpc[dt][1][tile][0]);
+            report(same, dt, tile, 0, 2);
+        }
+    for (const auto& T : kD3Tables)
+        for (int i = 0; i < T.n; ++i)
+            for (int t = 0; t < 2; ++t) on(T.rows[i][t]);
+    // where a slot serves both 16-bit types the launches have always used the fp16 instance's figure: bf16 is enabled only
+    for (int slot = 0; slot < 3; ++slot) {
+        on(gconv_kernel(PCV_BF16, slot));
+        on(gconv_kernel(PCV_F16, slot), &ctx->gconv_bpc[slot]);
+    }
+    for (int dt = PCV_BF16; dt <= PCV_F16; ++dt)
+        for (int s = 1; s <= 2; ++s)
+            for (int kt = 5; kt <= 9; kt += 4) on(gconvr_kernel(dt, s, kt));
+    for (int t = 0; t < 2; ++t)
+        for (int nchw = 0; nchw < 2; ++nchw)
+            for (int form = 0; form < 3; ++form) on(kStem[t][nchw][form], (nchw == 0 && form == STEM_PLAIN) ? &ctx->stem_bpc[t] : nullptr);
+    for (int form = 0; form < 4; ++form) {
+        on(kPair[0][form]);
+        on(kPair[1][form], form == PAIR_GATED ? nullptr : form == PAIR_IDCONV ? &ctx->pair_idc_bpc : &ctx->pair_bpc[form]);
+    }
+    for (int cfg = 0; cfg < 4; ++cfg)
+        for (int gated = 0; gated < 2; ++gated) {
+            on(wpair_launch(cfg, PCV_BF16, gated != 0).k);
+            on(wpair_launch(cfg, PCV_F16, gated != 0).k, gated ? nullptr : &ctx->wpair_bpc[cfg]);
+        }
     for (int dt = PCV_BF16; dt <= PCV_F16; ++dt)
         for (int s = 1; s <= 2; ++s)
             for (int e = 0; e < 2; ++e)
-                for (int rt = 2; rt <= 6; rt += 4)
-                    HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(pick_mbconv(dt, s, e != 0, rt)),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, kMbMaxLds));
-    for (const MbwEntry& e : kMbw)
-        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(e.fn), hipFuncAttributeMaxDynamicSharedMemorySize, kMbwMaxLds));
-    for (const MbrEntry& e : kMbr)
-        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(e.fn), hipFuncAttributeMaxDynamicSharedMemorySize, kMbwMaxLds));
-    return PCV_OK;
+                for (int rt = 2; rt <= 6; rt += 4) on(mbconv_kernel(dt, s, e != 0, rt));
+    for (const MbwEntry& e : kMbw) on(mbw_kernel_of(e));
+    for (const MbrEntry& e : kMbr) on(mbr_kernel_of(e));
+    return rc;
 }
 // Shapes the wave-private kernel (mbw.hpp) runs: an expand convolution with one K step (Cin <= 32: any stride, <= 64 projected
 // channels, weights in LDS) or two (Cin <= 64: stride 1, <= 64 projected channels, weights stay in L2).
 // ... or, WIDE units (pcv_set_tuning("mbw_wide", 0) = off): 65..96 projected channels with two or three K steps at stride 1, on wave
 // tiles of 2 pixel blocks (rb = 2) of 1 x 16 pixels.
-static int g_mbw_wide = 1;                                                          // process-wide: the `supported` query has no context
 static bool mbw_shape(int Cin, int Cout, int stride, int H, int W, int* ka_out, int* nrt_out, int* rb_out = nullptr) {
     const int ka = (Cin + 31) / 32, nrt = Cout <= 32 ? 2 : (Cout <= 64 ? 4 : 6);
     if (ka_out) *ka_out = ka;
@@ -768,12 +743,6 @@ static bool mbw_shape(int Cin, int Cout, int stride, int H, int W, int* ka_out, 
 // de: expand 1x1 (may be null), dd: depthwise 3x3, dp: project 1x1
 static const char* mbconv_unsupported(const pcv_conv_desc* de, const pcv_conv_desc& dd, const pcv_conv_desc& dp) {
     if ((de && desc_stale(*de)) || desc_stale(dd) || desc_stale(dp)) return kStaleDesc;
-    auto plain1x1 = [](const pcv_conv_desc& d) {
-        return d.kh == 1 && d.kw == 1 && d.stride_h == 1 && d.stride_w == 1 && d.pad_t == 0 && d.pad_l == 0 && d.pad_b == 0 &&
-               d.pad_r == 0 && d.groups == 1 && d.dil_h == 1 && d.dil_w == 1 && d.out_dtype == d.dtype &&
-               (d.x_cpitch == 0 || d.x_cpitch == d.Cin) && (d.x_wpitch == 0 || d.x_wpitch == d.W) &&
-               (d.y_cpitch == 0 || d.y_cpitch == d.Cout);
-    };
     if (dd.dtype != PCV_BF16 && dd.dtype != PCV_F16) return "16-bit storage only";
     if (dd.kh != 3 || dd.kw != 3 || dd.dil_h != 1 || dd.dil_w != 1 || dd.pad_t != 1 || dd.pad_l != 1 || dd.pad_b != 1 ||
         dd.pad_r != 1 || dd.stride_h != dd.stride_w || (dd.stride_h != 1 && dd.stride_h != 2) || dd.groups != dd.Cin ||
@@ -782,7 +751,7 @@ static const char* mbconv_unsupported(const pcv_conv_desc* de, const pcv_conv_de
         return "depthwise stage must be 3x3, pad 1, stride 1 or 2, no residual";
     const int Cmid = dd.Cin;
     if (Cmid % 8 != 0) return "expanded channels must be a multiple of 8";
-    if (!plain1x1(dp) || dp.dtype != dd.dtype || dp.Cin != Cmid || dp.Cout % 8 != 0 || dp.Cout > 96) return "project stage must be a plain 1x1 with at most 96 channels";
+    if (!plain_1x1(dp) || dp.dtype != dd.dtype || dp.Cin != Cmid || dp.Cout % 8 != 0 || dp.Cout > 96) return "project stage must be a plain 1x1 with at most 96 channels";
     // measured (MobileNetV2, batch 512): the fused unit wins on the large maps (the expanded tensor is what costs) and loses on
     // 14x14 and below / wide projections, where the three separate launches are cheap and this kernel is VALU-bound
     // the wave-private kernel (mbw.hpp: at most 32 unit inputs, one expand K step) also takes 64 projected channels and 14x14 maps
@@ -793,7 +762,7 @@ static const char* mbconv_unsupported(const pcv_conv_desc* de, const pcv_conv_de
     if (Wo < (wave_tiles ? 14 : 24) || Ho < 8) return "map too small for the fused unit to pay";
     int ka = 0;
     if (de) {
-        if (!plain1x1(*de) || de->dtype != dd.dtype || de->Cout != Cmid || de->Cin % 8 != 0 || de->has_residual ||
+        if (!plain_1x1(*de) || de->dtype != dd.dtype || de->Cout != Cmid || de->Cin % 8 != 0 || de->has_residual ||
             de->N != dd.N || de->H != dd.H || de->W != dd.W)
             return "expand stage must be a plain 1x1 onto the depthwise input";
         ka = (de->Cin + 31) / 32;
@@ -806,7 +775,7 @@ static const char* mbconv_unsupported(const pcv_conv_desc* de, const pcv_conv_de
     } else if (mbconv_plan(dd.stride_h, de != nullptr, ka, (Cmid + 31) / 32, (dp.Cout + 31) / 32 * 2, &nbuf).total > kMbMaxLds)
         return "weights + tiles do not fit the LDS budget";
     const long cin = de ? de->Cin : Cmid;
-    if ((long)dd.N * dd.H * dd.W * cin * 2 >= (1L << 31) || (long)dd.N * Ho * Wo * dp.Cout * 2 >= (1L << 31)) return "tensor exceeds the 2 GiB window";
+    if ((long)dd.N * dd.H * dd.W * cin * 2 >= (1L << 31) || (long)dd.N * Ho * Wo * dp.Cout * 2 >= (1L << 31)) return kTensorTooLarge;
     return nullptr;
 }
 
@@ -869,13 +838,7 @@ int pcv_create(pcv_ctx** out, int device) {
     ctx->num_cu = prop.multiProcessorCount;
     if (const char* e = std::getenv("PCV_AMD_PERSIST")) ctx->persist_mode = std::atoi(e);
     if (const char* e = std::getenv("PCV_AMD_PERSIST_NK")) ctx->persist_max_nk = std::atoi(e);
-    int rc = enable_big_lds(ctx);
-    if (rc == PCV_OK) rc = enable_d3x3(ctx);
-    if (rc == PCV_OK) rc = enable_gconv(ctx);
-    if (rc == PCV_OK) rc = enable_gconvr(ctx);
-    if (rc == PCV_OK) rc = enable_stem(ctx);
-    if (rc == PCV_OK) rc = enable_pair(ctx);
-    if (rc == PCV_OK) rc = enable_mbconv(ctx);
+    int rc = enable_kernels(ctx);
     if (rc == PCV_OK) {
         hipError_t e = hipMalloc(reinterpret_cast<void**>(&ctx->ovf), 256);
         if (e == hipSuccess) e = hipMemset(ctx->ovf, 0, 256);
@@ -895,30 +858,26 @@ int pcv_create(pcv_ctx** out, int device) {
 
 // Tuning/debug switches (same keys as the PCV_AMD_* environment variables read by pcv_create); not part of the
 // reference-facing contract. Returns PCV_ERR_INVALID for an unknown key.
+static const struct { const char* key; int pcv_ctx::*field; } kTuningKeys[] = {
+    {"persist", &pcv_ctx::persist_mode}, {"persist_nk", &pcv_ctx::persist_max_nk}, {"tile", &pcv_ctx::force_tile},
+    {"pair_pb", &pcv_ctx::pair_pb},      {"max_blocks", &pcv_ctx::max_blocks},     {"d3x3", &pcv_ctx::use_d3x3},
+    {"d3w", &pcv_ctx::use_d3w},          {"d3c", &pcv_ctx::use_d3c},               {"d3k", &pcv_ctx::use_d3k},
+    {"d3i", &pcv_ctx::use_d3i},          {"d1i", &pcv_ctx::use_d1i},               {"p1r", &pcv_ctx::use_p1r},
+    {"head", &pcv_ctx::use_head},        {"stem32", &pcv_ctx::use_stem32},         {"d1x1", &pcv_ctx::use_d1x1},
+    {"gconvr", &pcv_ctx::use_gconvr},    {"mbw", &pcv_ctx::use_mbw},               {"mbr", &pcv_ctx::use_mbr},
+    {"mbr_xl", &pcv_ctx::use_mbr_xl},    {"dw_th", &pcv_ctx::dw_th},               {"dw_flags", &pcv_ctx::dw_flags},
+    {"wstat", &pcv_ctx::use_wstat},
+};
 int pcv_set_tuning(pcv_ctx* ctx, const char* key, int value) {
     if (!ctx || !key) return PCV_ERR_INVALID;
     const std::string k(key);
-    if (k == "persist") ctx->persist_mode = value;
-    else if (k == "persist_nk") ctx->persist_max_nk = value;
-    else if (k == "tile") ctx->force_tile = value;
-    else if (k == "pair_pb") ctx->pair_pb = value;
-    else if (k == "mbw_wide") g_mbw_wide = value;           // process-wide, as "wpair"
-    else if (k == "wpair") g_wpair_mask = value;            // process-wide: the `supported` query has no context argument
-    else if (k == "max_blocks") ctx->max_blocks = value;
-    else if (k == "d3x3") ctx->use_d3x3 = value;
-    else if (k == "d3w") ctx->use_d3w = value;
-    else if (k == "d3c") ctx->use_d3c = value;
-    else if (k == "d3k") ctx->use_d3k = value;
-    else if (k == "d3i") ctx->use_d3i = value;
-    else if (k == "d1i") ctx->use_d1i = value;
-    else if (k == "p1r") ctx->use_p1r = value;
-    else if (k == "head") ctx->use_head = value;
-    else if (k == "stem32") ctx->use_stem32 = value;
-    else if (k == "d1x1") ctx->use_d1x1 = value;
-    else if (k == "gconvr") ctx->use_gconvr = value;
-    else if (k == "mbw") ctx->use_mbw = value;
-    else if (k == "mbr") ctx->use_mbr = value;
-    else if (k == "mbr_xl") g_mbr_xl = value;
+    for (const auto& t : kTuningKeys)
+        if (k == t.key) {
+            ctx->*t.field = value;
+            return PCV_OK;
+        }
+    if (k == "mbw_wide") g_mbw_wide = value;                // these two: process-wide (see their definition)
+    else if (k == "wpair") g_wpair_mask = value;
     else if (k == "dbg") {
 #ifdef PCV_DBG_FLAGS
         ctx->dbg_flags = value;
@@ -927,11 +886,8 @@ int pcv_set_tuning(pcv_ctx* ctx, const char* key, int value) {
             return fail(ctx, PCV_ERR_INVALID, "pcv_set_tuning: \"dbg\" (timing experiments that produce wrong results) needs a -DPCV_DBG_FLAGS build");
 #endif
     }
-    else if (k == "dw_th") ctx->dw_th = value;
-    else if (k == "dw_flags") ctx->dw_flags = value;
     else if (k == "dbg_lo") ctx->dbg_ptr = (ctx->dbg_ptr & 0xFFFFFFFF00000000ull) | (unsigned)value;
     else if (k == "dbg_hi") ctx->dbg_ptr = (ctx->dbg_ptr & 0xFFFFFFFFull) | ((unsigned long long)(unsigned)value << 32);
-    else if (k == "wstat") ctx->use_wstat = value;
     else return fail(ctx, PCV_ERR_INVALID, "pcv_set_tuning: unknown key " + k);
     return PCV_OK;
 }
@@ -1329,7 +1285,7 @@ static ConvRoute route_conv(const pcv_ctx* ctx, const pcv_conv_desc* d, const Co
         if (P.d3i && ctx->use_d3i != 0 && (ctx->use_d3x3 < 0 || ctx->use_d3i > 0) && (ctx->use_d3w <= 0 || ctx->use_d3i > 0) &&
             d->H <= d3i_maxw && d->W <= d3i_maxw && G.cpitch == d->Cin && G.wpitch == d->W) {
             const long long tiles = (long long)((d->Cout + D3ICfg::BM - 1) / D3ICfg::BM) * ((d->N + d3i_nimg - 1) / d3i_nimg);
-            // (almost) full pixel blocks: more than 12 of 13 / 6 of 7 blocks' worth of pixels
+            // (almost) full pixel blocks: more than 11 of 13 / 5 of 7 blocks' worth of pixels
             const bool full = d3i_nimg * d->H * d->W > 16 * ((d->Cin == 256 ? D3ICfgT<256>::NBLK : D3ICfgT<512>::NBLK) - 1) - 16;
             if (ctx->use_d3i > 0 || (full && 4 * tiles >= 3ll * ctx->num_cu)) { R.kernel = CK_D3I; return R; }
         }
@@ -1359,7 +1315,7 @@ static ConvRoute route_conv(const pcv_ctx* ctx, const pcv_conv_desc* d, const Co
             // 256 input channels: 64 channels per wave (groups of 512) unless the layer has a skip tensor (whose pieces only fit beside 32
             // channels' weights) or too few channels for 3/4 of such a group
             const int shape = d->Cin == 512 ? 1 : ((d->has_residual || d->Cout < 384) ? 2 : 0);
-            const D3Shape& S = kP1R[shape];
+            const Kernel& S = kP1R[shape][0];
             const long long groups = (d->Cout + S.BM - 1) / S.BM, tiles = ((long long)G.M64 + S.BP - 1) / S.BP * groups;
             if (ctx->use_p1r > 0 || (d->Cout * 4 >= groups * S.BM * 3 && tiles >= 2ll * block_slots(ctx, 1))) {
                 R.kernel = CK_P1R;
@@ -1387,8 +1343,7 @@ static int launch_stem(pcv_ctx* ctx, const pcv_conv_desc* d, const ConvPlan& P, 
     q.Hq = pool ? pool_out(P.Ho, 3, 2, 1, 0) : P.Ho;
     q.Wq = pool ? pool_out(P.Wo, 3, 2, 1, 0) : P.Wo;
     const unsigned long long ybytes = (unsigned long long)d->N * q.Hq * q.Wq * (unsigned long long)d->Cout * P.ES;
-    if (ybytes >= 0x80000000ull)
-        return fail(ctx, PCV_ERR_TOO_LARGE, "pcv_conv2d_fused: output exceeds the 2 GiB window of one launch; split the batch");
+    if (!in_window(ybytes)) return too_large(ctx, "pcv_conv2d_fused", "output");
     q.y_bytes = (uint32_t)ybytes;
     q.N = d->N; q.H = d->H; q.W = d->W; q.Wp = G.wpitch; q.Ho = P.Ho; q.Wo = P.Wo; q.Cout = d->Cout;
     q.kh = d->kh; q.pt = d->pad_t; q.x0off = -(d->pad_l + (d->pad_l & 1));
@@ -1400,32 +1355,12 @@ static int launch_stem(pcv_ctx* ctx, const pcv_conv_desc* d, const ConvPlan& P, 
     q.act = d->act;
     if (d->has_residual || d->post_act != PCV_ACT_NONE)
         return fail(ctx, PCV_ERR_INVALID, "pcv_conv2d_fused: the stem kernel has no residual / post-activation path");
-    long long nb = block_slots(ctx, g_stem_blocks_per_cu[d->dtype == PCV_BF16 ? 0 : 1]);
+    const int t = d->dtype == PCV_BF16 ? 0 : 1;
+    long long nb = block_slots(ctx, ctx->stem_bpc[t]);
     if (nb > nT) nb = nT;
     nb = (nb + 7) / 8 * 8;
-    const bool bf = d->dtype == PCV_BF16;
-    const dim3 g((unsigned)nb), b(256);
-    hipStream_t st = A.stream;
     const bool narrow = !pool && d->Cout <= 32 && ctx->use_stem32;             // half the channel rows: stems of the MobileNet / EfficientNet families
-    if (narrow && x_nchw) {
-        const int lds = kStemLds + kStemStageBytes;
-        if (bf) hipLaunchKernelGGL((stem_conv_kernel<PCV_BF16, false, true, 2>), g, b, lds, st, q);
-        else hipLaunchKernelGGL((stem_conv_kernel<PCV_F16, false, true, 2>), g, b, lds, st, q);
-    } else if (narrow) {
-        if (bf) hipLaunchKernelGGL((stem_conv_kernel<PCV_BF16, false, false, 2>), g, b, kStemLds, st, q);
-        else hipLaunchKernelGGL((stem_conv_kernel<PCV_F16, false, false, 2>), g, b, kStemLds, st, q);
-    } else if (x_nchw) {
-        const int lds = kStemLds + kStemStageBytes;
-        if (pool && bf) hipLaunchKernelGGL((stem_conv_kernel<PCV_BF16, true, true>), g, b, lds, st, q);
-        else if (pool) hipLaunchKernelGGL((stem_conv_kernel<PCV_F16, true, true>), g, b, lds, st, q);
-        else if (bf) hipLaunchKernelGGL((stem_conv_kernel<PCV_BF16, false, true>), g, b, lds, st, q);
-        else hipLaunchKernelGGL((stem_conv_kernel<PCV_F16, false, true>), g, b, lds, st, q);
-    } else if (pool && bf) hipLaunchKernelGGL((stem_conv_kernel<PCV_BF16, true>), g, b, kStemLds, st, q);
-    else if (pool) hipLaunchKernelGGL((stem_conv_kernel<PCV_F16, true>), g, b, kStemLds, st, q);
-    else if (bf) hipLaunchKernelGGL((stem_conv_kernel<PCV_BF16, false>), g, b, kStemLds, st, q);
-    else hipLaunchKernelGGL((stem_conv_kernel<PCV_F16, false>), g, b, kStemLds, st, q);
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    return launch(ctx, kStem[t][x_nchw ? 1 : 0][narrow ? STEM_NARROW : (pool ? STEM_POOLED : STEM_PLAIN)], (unsigned)nb, A.stream, q);
 }
 
 static int launch_gconv_rows(pcv_ctx* ctx, const pcv_conv_desc* d, const ConvPlan& P, const ConvGeom& G, const ConvArgs& A,
@@ -1448,12 +1383,10 @@ static int launch_gconv_rows(pcv_ctx* ctx, const pcv_conv_desc* d, const ConvPla
     q.nTiles = (int)nT;
     q.act = d->act;
     const int lds = 2 * gr.xl * 32 * 128;
-    long long nb = block_slots(ctx, lds * 2 <= 160 * 1024 ? 2 : 1);
+    long long nb = block_slots(ctx, lds * 2 <= kGconvRMaxLds ? 2 : 1);
     if (nb > nT) nb = nT;
     nb = (nb + 7) / 8 * 8;
-    hipLaunchKernelGGL(pick_gconvr(d->dtype, d->stride_h, P.gconv_kt), dim3((unsigned)nb), dim3(256), lds, A.stream, q);
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    return launch(ctx, gconvr_kernel(d->dtype, d->stride_h, P.gconv_kt, lds), (unsigned)nb, A.stream, q);
 }
 
 static int launch_gconv_flat(pcv_ctx* ctx, const pcv_conv_desc* d, const ConvPlan& P, const ConvGeom& G, const ConvArgs& A) {
@@ -1471,36 +1404,59 @@ static int launch_gconv_flat(pcv_ctx* ctx, const pcv_conv_desc* d, const ConvPla
     if (nT >= 0x7FFFFFFFll) return fail(ctx, PCV_ERR_TOO_LARGE, "pcv_conv2d_fused: too many tiles; split the batch");
     q.nTiles = (int)nT;
     q.act = d->act;
-    const GConvLaunch L = pick_gconv(d->dtype, d->W);
-    const int wi = d->W + 1 <= 16 ? 0 : (d->W + 1 <= 32 ? 1 : 2);
-    long long nb = block_slots(ctx, g_gconv_blocks_per_cu[wi]);
+    const int slot = gconv_slot(d->W);
+    long long nb = block_slots(ctx, ctx->gconv_bpc[slot]);
     if (nb > nT) nb = nT;
     nb = (nb + 7) / 8 * 8;
-    hipLaunchKernelGGL(L.fn, dim3((unsigned)nb), dim3(256), L.lds, A.stream, q);
-    HIP_TRY(ctx, hipGetLastError());
+    return launch(ctx, gconv_kernel(d->dtype, slot), (unsigned)nb, A.stream, q);
+}
+
+// y's channel pitch in elements (y_cpitch, 0 = dense) and its extent in bytes. Y_ALIGNED: every pixel's channels start on 16 bytes;
+// Y_DENSE_ANY: a dense y (pitch == Cout) may also have any channel count (the generic kernel's ragged variants)
+enum YPitchRule { Y_ALIGNED, Y_DENSE_ANY };
+static int y_pitch(pcv_ctx* ctx, const pcv_conv_desc* d, const ConvGeom& G, YPitchRule rule, int* ypitch, unsigned long long* ybytes) {
+    const int es = esize(d->out_dtype);
+    *ypitch = d->y_cpitch > 0 ? d->y_cpitch : d->Cout;
+    if (*ypitch < d->Cout || (!(rule == Y_DENSE_ANY && *ypitch == d->Cout) && (*ypitch * es) % 16 != 0))
+        return fail(ctx, PCV_ERR_INVALID, "pcv_conv2d_fused: y_cpitch must be >= Cout and a multiple of 16 bytes");
+    *ybytes = ((G.M64 - 1) * (unsigned long long)*ypitch + d->Cout) * es;
     return PCV_OK;
 }
 
-// d3q_kernel, both modes: `one` = the 1x1 mode (kD1 shapes; H / W / HW describe the OUTPUT map, a strided 1x1 reads every
-// stride-th pixel), else the dense 3x3 mode (kD3 shapes)
-static int launch_d3q(pcv_ctx* ctx, const pcv_conv_desc* d, const ConvPlan& P, const ConvGeom& G, const ConvArgs& A, int shape, bool one,
-                      bool wide = false, bool c64 = false, bool p1r = false) {
-    const int ypitch = d->y_cpitch > 0 ? d->y_cpitch : d->Cout;
-    const unsigned long long ybytes = ((G.M64 - 1) * (unsigned long long)ypitch + d->Cout) * 2ull;
-    if (ypitch < d->Cout || (ypitch * 2) % 16 != 0)
-        return fail(ctx, PCV_ERR_INVALID, "pcv_conv2d_fused: y_cpitch must be >= Cout and a multiple of 16 bytes");
-    if (ybytes >= 0x80000000ull)
-        return fail(ctx, PCV_ERR_TOO_LARGE, "pcv_conv2d_fused: output exceeds the 2 GiB window of one launch; split the batch");
-    static const D3Shape kC64 = {D3CCfg::BM, D3CCfg::BP, D3CCfg::LDS, {kD3C[0], kD3C[1]}};
-    static const D3Shape kC128 = {D3KCfg::BM, D3KCfg::BP, D3KCfg::LDS, {kD3K[0], kD3K[1]}};      // (c64 with shape 1: d3k_kernel, the same tile scheme)
-    // wide: d3w_kernel (512 threads); c64: d3c_kernel (256 threads, tiles = 4 output rows of one image); same parameter block
-    // p1r: p1r_kernel (512 threads; 1x1 mode of the parameter block, channel "tiles" = groups of 512 / 256 channels)
-    const D3Shape& S = p1r ? kP1R[shape] : (c64 ? (shape == 1 ? kC128 : kC64) : (wide ? kD3W[shape] : (one ? kD1[shape] : kD3[shape])));
+static const Kernel kNoKernel = {nullptr, 0, 0, 0, 0};
+static const Kernel& d3_kernel(const ConvRoute& R, const pcv_conv_desc* d) {
+    const int t = d->dtype == PCV_BF16 ? 0 : 1;
+    switch (R.kernel) {
+        case CK_D3C: return kD3C[0][t];
+        case CK_D3K: return kD3K[0][t];
+        case CK_D3I: return kD3I[d->Cin == 256 ? 0 : 1][t];
+        case CK_D1I: return kD1I[d->Cin == 1024 ? 0 : 1][t];
+        case CK_D3W: return kD3W[R.shape][t];
+        case CK_P1R: return kP1R[R.shape][t];
+        case CK_D3Q_1X1: return kD1[R.shape][t];
+        case CK_D3Q: return kD3[R.shape][t];
+        default: return kNoKernel;              // not a D3Params kernel
+    }
+}
+// Every kernel that takes D3Params (CK_D3I .. CK_D3Q_1X1; all 16 bit): the dense 3x3 ones and, with the parameter block in its 1x1 mode
+// (H / W / HW describe the OUTPUT map, a strided 1x1 reads every stride-th pixel), p1r / d1i / d3q's 1x1 shapes
+static int launch_d3(pcv_ctx* ctx, const pcv_conv_desc* d, const ConvPlan& P, const ConvGeom& G, const ConvArgs& A, const ConvRoute& R) {
+    const ConvKernel ck = R.kernel;
+    const Kernel& K = d3_kernel(R, d);
+    if (!K.fn) return fail(ctx, PCV_ERR_INVALID, "pcv_conv2d_fused: no kernel for this route");
+    const bool one = ck == CK_P1R || ck == CK_D1I || ck == CK_D3Q_1X1;
+    const bool own_blob = ck == CK_D3I || ck == CK_D1I;       // the fragment-ordered copy behind the generic blob (ConvPlan::d3i_off)
+    int ypitch = 0;
+    unsigned long long ybytes = 0;
+    if (int rc = y_pitch(ctx, d, G, Y_ALIGNED, &ypitch, &ybytes)) return rc;
+    if (!in_window(ybytes)) return too_large(ctx, "pcv_conv2d_fused", "output");
     D3Params q;
     std::memset(&q, 0, sizeof(q));
-    q.x = A.x; q.w = static_cast<const char*>(A.packed) + P.ktab_bytes; q.res = d->has_residual ? A.residual : nullptr; q.y = A.y;
-    q.scale = A.scale; q.shift = A.shift; q.ovf = ctx->ovf; q.dbgflags = ctx->dbg_flags;
-    q.x_bytes = (uint32_t)G.xbytes; q.w_bytes = (uint32_t)P.w_bytes; q.y_bytes = (uint32_t)ybytes;
+    q.x = A.x; q.res = d->has_residual ? A.residual : nullptr; q.y = A.y;
+    q.w = static_cast<const char*>(A.packed) + (own_blob ? P.d3i_off : P.ktab_bytes);
+    q.scale = A.scale; q.shift = A.shift; q.ovf = ctx->ovf;
+    if (!own_blob) q.dbgflags = ctx->dbg_flags;
+    q.x_bytes = (uint32_t)G.xbytes; q.w_bytes = (uint32_t)(own_blob ? P.total_bytes - P.d3i_off : P.w_bytes); q.y_bytes = (uint32_t)ybytes;
     q.res_bytes = (uint32_t)(G.M64 * (unsigned long long)d->Cout * 2ull);
     q.M = (int)G.M64; q.Cout = d->Cout; q.Ypitch = ypitch; q.Cin = d->Cin; q.Kpad = P.Kpad;
     q.Hin = d->H; q.Win = d->W;
@@ -1509,102 +1465,50 @@ static int launch_d3q(pcv_ctx* ctx, const pcv_conv_desc* d, const ConvPlan& P, c
         q.div_w = make_fastdiv((uint32_t)P.Wo);
         q.stride = d->stride_h;
         q.nk = d->Cin / 64; q.slices = q.nk;
-        if (p1r) q.dbg = reinterpret_cast<uint32_t*>(ctx->dbg_ptr);       // (diagnostic builds: -DP1R_CYCLES)
     } else {
         q.H = d->H; q.W = d->W; q.HW = d->H * d->W;
         q.div_w = make_fastdiv((uint32_t)d->W);
         q.stride = 1;
         q.nk = P.nk; q.slices = d->Cin / 64;
-        q.dbg = reinterpret_cast<uint32_t*>(ctx->dbg_ptr);       // (diagnostic builds: -DD3X3_STAMPS, -DD3W_CYCLES, -DD3C_CYCLES)
     }
+    // (diagnostic builds: -DD3X3_STAMPS, -DD3W_CYCLES, -DD3C_CYCLES, -DD3I_CYCLES, -DD1I_CYCLES, -DP1R_CYCLES; d3q's 1x1 shapes have none)
+    if (ck != CK_D3Q_1X1) q.dbg = reinterpret_cast<uint32_t*>(ctx->dbg_ptr);
     q.div_hw = make_fastdiv((uint32_t)q.HW);
     q.act = d->act; q.post_act = d->post_act;
-    q.nChTiles = (d->Cout + S.BM - 1) / S.BM;
-    // (c64 covers both register-weight kernels: d3c tiles D3CCfg::ROWS image rows, d3k D3KCfg::ROWS - route_conv counts with each one's own)
-    static_assert(D3CCfg::ROWS == D3KCfg::ROWS, "launch_d3q computes the tile count of d3c AND d3k from one ROWS constant");
-    const long long nT = c64 ? (long long)d->N * ((d->H + D3CCfg::ROWS - 1) / D3CCfg::ROWS) * q.nChTiles
-                             : ((long long)((G.M64 + S.BP - 1) / S.BP)) * q.nChTiles;
+    q.nChTiles = (d->Cout + K.BM - 1) / K.BM;
+    static_assert(D3CCfg::ROWS == D3KCfg::ROWS, "launch_d3 computes the tile count of d3c AND d3k from one ROWS constant");
+    long long nT;
+    switch (ck) {
+        case CK_D3C:            // tiles = ROWS output rows of one image (route_conv counts with each kernel's own constant)
+        case CK_D3K:
+            nT = (long long)d->N * ((d->H + D3CCfg::ROWS - 1) / D3CCfg::ROWS) * q.nChTiles;
+            break;
+        case CK_D3I: {          // one block per (image, or two 7 x 7 images; 256-channel tile)
+            const int nimg = d->Cin == 256 ? D3ICfgT<256>::NIMG : D3ICfgT<512>::NIMG;
+            nT = (long long)((d->N + nimg - 1) / nimg) * q.nChTiles;
+            break;
+        }
+        default: nT = ((long long)((G.M64 + K.BP - 1) / K.BP)) * q.nChTiles;       // (d1i: channel tiles of a pixel tile side by side)
+    }
     if (nT >= 0x7FFFFFFFll) return fail(ctx, PCV_ERR_TOO_LARGE, "pcv_conv2d_fused: too many tiles; split the batch");
     q.nTiles = (int)nT;
-    const long long slots = block_slots(ctx, 1);
-    long long nb = slots < nT ? slots : nT;
-    nb = (nb + 7) / 8 * 8;
-    if (p1r && nT > nb) {
+    long long nb = nT;          // d3i / d1i: one block per tile
+    if (!own_blob) {            // the others: a persistent grid of one block per CU, a multiple of 8 so that every XCD gets the same number
+        const long long slots = block_slots(ctx, 1);
+        nb = slots < nT ? slots : nT;
+        nb = (nb + 7) / 8 * 8;
+    }
+    if (ck == CK_P1R && nT > nb) {
         // p1r: equal tiles on a persistent grid leave the last round partly empty (12.25 rounds = 13). When the remainder splits evenly -
         // its tiles into 16-pixel units, one per block, every block getting a unit of its own channel group - the kernel runs it as
         // one-unit pseudo tiles behind the full rounds (p1r_conv.hpp, `tailN`).
-        const long long nCG = q.nChTiles, TP = S.BP / 16, rem = nT % nb;
+        const long long nCG = q.nChTiles, TP = K.BP / 16, rem = nT % nb;
         if (rem > 0 && nb % (8 * nCG) == 0 && rem % nCG == 0 && rem * TP <= nb && ctx->use_p1r != 3 && ctx->use_p1r != -3) {        // ("p1r" = 3 / -3: forced / automatic routing without the split tail, for A/B)
             q.nTiles = (int)(nT - rem);
             q.tailN = (int)rem;
         }
     }
-    void* args[] = {&q};
-    HIP_TRY(ctx, hipLaunchKernel(S.fn[d->dtype == PCV_BF16 ? 0 : 1], dim3((unsigned)nb), dim3(c64 ? 256 : ((wide || p1r) ? 512 : 768)), args, (size_t)S.lds, A.stream));
-    return PCV_OK;
-}
-
-// d3i_kernel: one block per (image, 256-channel tile); the parameter block of the other dense 3x3 kernels
-static int launch_d3i(pcv_ctx* ctx, const pcv_conv_desc* d, const ConvPlan& P, const ConvGeom& G, const ConvArgs& A) {
-    const int ypitch = d->y_cpitch > 0 ? d->y_cpitch : d->Cout;
-    const unsigned long long ybytes = ((G.M64 - 1) * (unsigned long long)ypitch + d->Cout) * 2ull;
-    if (ypitch < d->Cout || (ypitch * 2) % 16 != 0)
-        return fail(ctx, PCV_ERR_INVALID, "pcv_conv2d_fused: y_cpitch must be >= Cout and a multiple of 16 bytes");
-    if (ybytes >= 0x80000000ull)
-        return fail(ctx, PCV_ERR_TOO_LARGE, "pcv_conv2d_fused: output exceeds the 2 GiB window of one launch; split the batch");
-    D3Params q;
-    std::memset(&q, 0, sizeof(q));
-    q.x = A.x; q.w = static_cast<const char*>(A.packed) + P.d3i_off; q.res = d->has_residual ? A.residual : nullptr; q.y = A.y;
-    q.scale = A.scale; q.shift = A.shift; q.ovf = ctx->ovf;
-    q.x_bytes = (uint32_t)G.xbytes; q.w_bytes = (uint32_t)(P.total_bytes - P.d3i_off); q.y_bytes = (uint32_t)ybytes;
-    q.res_bytes = (uint32_t)(G.M64 * (unsigned long long)d->Cout * 2ull);
-    q.M = (int)G.M64; q.Cout = d->Cout; q.Ypitch = ypitch; q.Cin = d->Cin; q.Kpad = P.Kpad;
-    q.H = d->H; q.W = d->W; q.HW = d->H * d->W; q.Hin = d->H; q.Win = d->W; q.stride = 1;
-    q.div_w = make_fastdiv((uint32_t)d->W);
-    q.div_hw = make_fastdiv((uint32_t)q.HW);
-    q.nk = P.nk; q.slices = d->Cin / 64;
-    q.act = d->act; q.post_act = d->post_act;
-    q.nChTiles = (d->Cout + D3ICfg::BM - 1) / D3ICfg::BM;
-    const int wide = d->Cin == 256 ? 0 : 1, nimg = wide ? D3ICfgT<512>::NIMG : D3ICfgT<256>::NIMG;
-    const long long nT = (long long)((d->N + nimg - 1) / nimg) * q.nChTiles;
-    if (nT >= 0x7FFFFFFFll) return fail(ctx, PCV_ERR_TOO_LARGE, "pcv_conv2d_fused: too many tiles; split the batch");
-    q.nTiles = (int)nT;
-    q.dbg = reinterpret_cast<uint32_t*>(ctx->dbg_ptr);       // (diagnostic builds: -DD3I_CYCLES)
-    void* args[] = {&q};
-    HIP_TRY(ctx, hipLaunchKernel(kD3I[wide][d->dtype == PCV_BF16 ? 0 : 1], dim3((unsigned)nT), dim3(D3ICfg::THREADS), args,
-                                 (size_t)(wide ? D3ICfgT<512>::LDS : D3ICfgT<256>::LDS), A.stream));
-    return PCV_OK;
-}
-
-// d1i_kernel: one block per (208-pixel tile, 256-channel tile), channel tiles of a pixel tile side by side
-static int launch_d1i(pcv_ctx* ctx, const pcv_conv_desc* d, const ConvPlan& P, const ConvGeom& G, const ConvArgs& A) {
-    const int ypitch = d->y_cpitch > 0 ? d->y_cpitch : d->Cout;
-    const unsigned long long ybytes = ((G.M64 - 1) * (unsigned long long)ypitch + d->Cout) * 2ull;
-    if (ypitch < d->Cout || (ypitch * 2) % 16 != 0)
-        return fail(ctx, PCV_ERR_INVALID, "pcv_conv2d_fused: y_cpitch must be >= Cout and a multiple of 16 bytes");
-    if (ybytes >= 0x80000000ull)
-        return fail(ctx, PCV_ERR_TOO_LARGE, "pcv_conv2d_fused: output exceeds the 2 GiB window of one launch; split the batch");
-    D3Params q;
-    std::memset(&q, 0, sizeof(q));
-    q.x = A.x; q.w = static_cast<const char*>(A.packed) + P.d3i_off; q.res = d->has_residual ? A.residual : nullptr; q.y = A.y;
-    q.scale = A.scale; q.shift = A.shift; q.ovf = ctx->ovf;
-    q.x_bytes = (uint32_t)G.xbytes; q.w_bytes = (uint32_t)(P.total_bytes - P.d3i_off); q.y_bytes = (uint32_t)ybytes;
-    q.res_bytes = (uint32_t)(G.M64 * (unsigned long long)d->Cout * 2ull);
-    q.M = (int)G.M64; q.Cout = d->Cout; q.Ypitch = ypitch; q.Cin = d->Cin; q.Kpad = P.Kpad;
-    q.H = d->H; q.W = d->W; q.HW = d->H * d->W; q.Hin = d->H; q.Win = d->W; q.stride = 1;
-    q.div_w = make_fastdiv((uint32_t)d->W);
-    q.div_hw = make_fastdiv((uint32_t)q.HW);
-    q.nk = d->Cin / 64; q.slices = q.nk;
-    q.act = d->act; q.post_act = d->post_act;
-    q.nChTiles = (d->Cout + 255) / 256;
-    const long long nT = ((long long)G.M64 + D1ICfgT<1024>::BP - 1) / D1ICfgT<1024>::BP * q.nChTiles;
-    if (nT >= 0x7FFFFFFFll) return fail(ctx, PCV_ERR_TOO_LARGE, "pcv_conv2d_fused: too many tiles; split the batch");
-    q.nTiles = (int)nT;
-    q.dbg = reinterpret_cast<uint32_t*>(ctx->dbg_ptr);       // (diagnostic builds: -DD1I_CYCLES)
-    void* args[] = {&q};
-    const int ci = d->Cin == 1024 ? 0 : 1;
-    HIP_TRY(ctx, hipLaunchKernel(kD1I[ci][d->dtype == PCV_BF16 ? 0 : 1], dim3((unsigned)nT), dim3(256), args, (size_t)D1ICfgT<1024>::LDS, A.stream));
-    return PCV_OK;
+    return launch(ctx, K, (unsigned)nb, A.stream, q);
 }
 
 // dense layer on a 1x1 map, fp32 (classifier): many small blocks instead of a handful of 128x128 tiles
@@ -1627,9 +1531,8 @@ static int launch_igemm(pcv_ctx* ctx, const pcv_conv_desc* d, const ConvPlan& P,
     if (R.special && P.ngb != 1 && ((d->Cout % 8 != 0) || (P.cout_blk % 8 != 0)))
         return fail(ctx, PCV_ERR_INVALID, "pcv_conv2d_fused: ragged channel count with groups unsupported");
     const int tile = R.tile, khw = R.khw;
-    igemm_fn fn = pick_igemm(d->dtype, d->out_dtype, R.special, tile, khw);
-    if (!fn) return fail(ctx, PCV_ERR_INVALID, "pcv_conv2d_fused: no kernel for this dtype combination");
-    const TileInfo& T = kTiles[tile];
+    const Kernel T = igemm_kernel(d->dtype, d->out_dtype, R.special, tile, khw);
+    if (!T.fn) return fail(ctx, PCV_ERR_INVALID, "pcv_conv2d_fused: no kernel for this dtype combination");
 
     IgemmParams p;
     p.x = A.x;
@@ -1643,15 +1546,11 @@ static int launch_igemm(pcv_ctx* ctx, const pcv_conv_desc* d, const ConvPlan& P,
     p.shift = A.shift;
     p.x_bytes = (uint32_t)G.xbytes;
     p.w_bytes = (uint32_t)P.w_bytes;
-    const int ypitch = d->y_cpitch > 0 ? d->y_cpitch : d->Cout;
-    if (ypitch < d->Cout || (ypitch != d->Cout && (ypitch * esize(d->out_dtype)) % 16 != 0))
-        return fail(ctx, PCV_ERR_INVALID, "pcv_conv2d_fused: y_cpitch must be >= Cout and a multiple of 16 bytes");
-    {
-        const unsigned long long ybytes = ((G.M64 - 1) * (unsigned long long)ypitch + d->Cout) * esize(d->out_dtype);
-        if (ybytes >= 0x80000000ull && d->out_dtype != PCV_F32)
-            return fail(ctx, PCV_ERR_TOO_LARGE, "pcv_conv2d_fused: output exceeds the 2 GiB window of one launch; split the batch");
-        p.y_bytes = ybytes >= 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)ybytes;
-    }
+    int ypitch = 0;
+    unsigned long long ybytes = 0;
+    if (int rc = y_pitch(ctx, d, G, Y_DENSE_ANY, &ypitch, &ybytes)) return rc;
+    if (!in_window(ybytes) && d->out_dtype != PCV_F32) return too_large(ctx, "pcv_conv2d_fused", "output");
+    p.y_bytes = ybytes >= 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)ybytes;
     p.M = (int)G.M64;
     p.Cout = P.cout_blk;
     p.Cout_total = d->Cout;
@@ -1688,18 +1587,15 @@ static int launch_igemm(pcv_ctx* ctx, const pcv_conv_desc* d, const ConvPlan& P,
     if (nTiles >= 0x7FFFFFFFll) return fail(ctx, PCV_ERR_TOO_LARGE, "pcv_conv2d_fused: too many tiles; split the batch");
     p.nTiles = (int)nTiles;
     // persistent grid: what is resident at once, a multiple of 8 so that every XCD gets the same number of blocks
-    const int bpc = R.special ? g_blocks_per_cu[d->dtype][1][tile][0] : g_blocks_per_cu[d->dtype][0][tile][khw_slot(khw)];
+    const int bpc = R.special ? ctx->igemm_bpc[d->dtype][1][tile][0] : ctx->igemm_bpc[d->dtype][0][tile][khw_slot(khw)];
     // Short K loops (HBM-bound 1x1 layers) run persistent, so that the next tile's loads overlap this tile's
     // epilogue; long K loops run one tile per block (the dispatcher refills a CU while the finished block's stores drain).
     const bool persistent = ctx->persist_mode == 1 || (ctx->persist_mode < 0 && P.nk <= ctx->persist_max_nk);
     long long nblocks = persistent ? block_slots(ctx, bpc) : nTiles;
     if (nblocks > nTiles) nblocks = nTiles;
     nblocks = (nblocks + 7) / 8 * 8;
-    dim3 grid((unsigned)nblocks);
     p.wstat = (ctx->use_wstat && persistent && P.nk == 1 && p.nChTiles == 1 && P.ngb == 1) ? 1 : 0;
-    hipLaunchKernelGGL(fn, grid, dim3(T.threads), T.lds, A.stream, p);
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    return launch(ctx, T, (unsigned)nblocks, A.stream, p);
 }
 
 static int conv2d_impl(pcv_ctx* ctx, const pcv_conv_desc* d, const void* x, const void* packed, const float* scale,
@@ -1722,8 +1618,7 @@ static int conv2d_impl(pcv_ctx* ctx, const pcv_conv_desc* d, const void* x, cons
     G.xbytes = (unsigned long long)d->N * d->H * G.wpitch * G.cpitch * P.ES;
     G.M64 = (unsigned long long)d->N * P.Ho * P.Wo;
     G.sliced_y = d->y_cpitch > 0 && d->y_cpitch != d->Cout;
-    if (G.xbytes >= 0x80000000ull || G.M64 >= 0x7FFFFFFFull)
-        return fail(ctx, PCV_ERR_TOO_LARGE, "pcv_conv2d_fused: input exceeds the 2 GiB window of one launch; split the batch");
+    if (!in_window(G.xbytes) || G.M64 >= 0x7FFFFFFFull) return too_large(ctx, "pcv_conv2d_fused", "input");
     if (!aligned16(x) || !aligned16(packed) || !aligned16(y) || (residual && !aligned16(residual)) ||
         (scale && !aligned16(scale)) || (shift && !aligned16(shift)))
         return fail(ctx, PCV_ERR_INVALID, "pcv_conv2d_fused: pointers must be 16-byte aligned");
@@ -1732,8 +1627,8 @@ static int conv2d_impl(pcv_ctx* ctx, const pcv_conv_desc* d, const void* x, cons
     if (pool && !P.stem) return fail(ctx, PCV_ERR_INVALID, "pcv_conv2d_maxpool_fused: only the stem convolution has a fused max-pool");
     if (x_nchw && (!P.stem || d->Cin > 3 || d->W % 4 != 0))
         return fail(ctx, PCV_ERR_INVALID, "pcv_conv2d_nchw_stem_fused: only the stem convolution (<= 3 input planes, W a multiple of 4)");
-    if (x_nchw && (unsigned long long)d->N * d->Cin * d->H * d->W * 4ull >= 0x80000000ull)
-        return fail(ctx, PCV_ERR_TOO_LARGE, "pcv_conv2d_nchw_stem_fused: the fp32 image batch exceeds the 2 GiB window of one launch; split the batch");
+    if (x_nchw && !in_window((unsigned long long)d->N * d->Cin * d->H * d->W * 4ull))
+        return too_large(ctx, "pcv_conv2d_nchw_stem_fused", "the fp32 image batch");
 
     const ConvArgs A{x, packed, scale, shift, residual, y, gate, (hipStream_t)stream, pool, x_nchw};
     const ConvRoute R = route_conv(ctx, d, P, G, A);
@@ -1741,14 +1636,8 @@ static int conv2d_impl(pcv_ctx* ctx, const pcv_conv_desc* d, const void* x, cons
         case CK_STEM: return launch_stem(ctx, d, P, G, A);
         case CK_GCONV_ROWS: return launch_gconv_rows(ctx, d, P, G, A, R.rows);
         case CK_GCONV_FLAT: return launch_gconv_flat(ctx, d, P, G, A);
-        case CK_D3C: return launch_d3q(ctx, d, P, G, A, 0, false, false, true);
-        case CK_D3K: return launch_d3q(ctx, d, P, G, A, 1, false, false, true);
-        case CK_D3I: return launch_d3i(ctx, d, P, G, A);
-        case CK_D1I: return launch_d1i(ctx, d, P, G, A);
-        case CK_D3W: return launch_d3q(ctx, d, P, G, A, R.shape, false, true);
-        case CK_D3Q: return launch_d3q(ctx, d, P, G, A, R.shape, false);
-        case CK_P1R: return launch_d3q(ctx, d, P, G, A, R.shape, true, false, false, true);
-        case CK_D3Q_1X1: return launch_d3q(ctx, d, P, G, A, R.shape, true);
+        case CK_D3I: case CK_D1I: case CK_D3K: case CK_D3C: case CK_D3W: case CK_D3Q: case CK_P1R: case CK_D3Q_1X1:
+            return launch_d3(ctx, d, P, G, A, R);                      // the kernels that take D3Params
         case CK_HEAD: return launch_head(ctx, d, P, G, A);
         default: return launch_igemm(ctx, d, P, G, A, R);
     }
@@ -1831,8 +1720,7 @@ int pcv_dwconv2d_fused(pcv_ctx* ctx, const pcv_conv_desc* d, const void* x, cons
     p.ovf = ctx->ovf;
     p.N = d->N; p.H = d->H; p.W = d->W; p.C = d->Cin;
     const unsigned long long xbytes = (unsigned long long)d->N * d->H * d->W * d->Cin * esize(d->dtype);
-    if (xbytes >= 0x80000000ull)
-        return fail(ctx, PCV_ERR_TOO_LARGE, "pcv_dwconv2d_fused: input exceeds the 2 GiB window of one launch; split the batch");
+    if (!in_window(xbytes)) return too_large(ctx, "pcv_dwconv2d_fused", "input");
     p.x_bytes = (uint32_t)xbytes;
     p.Ho = (d->H + d->pad_t + d->pad_b - (d->kh - 1) - 1) / d->stride_h + 1;
     p.Wo = (d->W + d->pad_l + d->pad_r - (d->kw - 1) - 1) / d->stride_w + 1;
@@ -2126,10 +2014,8 @@ static int pair_impl(pcv_ctx* ctx, const pcv_conv_desc* d1, const pcv_conv_desc*
         q.hw = (uint32_t)(d1->H * d1->W);
         q.M = (int)M; q.nTiles = (int)((M + L.tileP - 1) / L.tileP);
         q.act1 = d1->act; q.post1 = d1->post_act; q.act2 = d2->act;
-        const unsigned grid = (unsigned)std::min<long>(q.nTiles, (long)block_slots(ctx, g_wpair_blocks_per_cu[cfg]));
-        void* args[] = {&q};
-        HIP_TRY(ctx, hipLaunchKernel(L.fn, dim3(grid), dim3((unsigned)L.threads), args, (size_t)L.lds, st));
-        return PCV_OK;
+        const unsigned grid = (unsigned)std::min<long>(q.nTiles, (long)block_slots(ctx, ctx->wpair_bpc[cfg]));
+        return launch(ctx, L.k, grid, st, q);
     }
     if (P1.wrows != 256 || P1.Kpad != 64 || P2.wrows != 64 || P2.Kpad != 256 || P1.ngb != 1 || P2.ngb != 1)
         return fail(ctx, PCV_ERR_INVALID, "pcv_conv1x1_pair_fused: unexpected packed layout");
@@ -2144,34 +2030,19 @@ static int pair_impl(pcv_ctx* ctx, const pcv_conv_desc* d1, const pcv_conv_desc*
     const int pb = ctx->pair_pb == 4 ? 4 : 2;
     p.M = (int)M; p.nTiles = (int)((M + 16 * pb - 1) / (16 * pb));
     p.act1 = d1->act; p.post1 = d1->post_act; p.act2 = d2->act;
-    const unsigned grid = (unsigned)std::min<long>(p.nTiles, (long)block_slots(ctx, g_pair_blocks_per_cu[pb == 4 ? 0 : 1]));
     p.gate = gate;
     p.div_hw = make_fastdiv((uint32_t)(d1->H * d1->W));
-    if (gate) {
-        const unsigned ggrid = (unsigned)std::min<long>((M + 31) / 32, (long)block_slots(ctx, g_pair_blocks_per_cu[1]));
-        p.nTiles = (int)((M + 31) / 32);
-        if (d1->dtype == PCV_BF16) pair1x1_kernel<PCV_BF16, 2, false, true><<<ggrid, 256, pair_lds(2), st>>>(p);
-        else pair1x1_kernel<PCV_F16, 2, false, true><<<ggrid, 256, pair_lds(2), st>>>(p);
-    } else if (pb == 4) {
-        if (d1->dtype == PCV_BF16) pair1x1_kernel<PCV_BF16, 4><<<grid, 256, pair_lds(4), st>>>(p);
-        else pair1x1_kernel<PCV_F16, 4><<<grid, 256, pair_lds(4), st>>>(p);
-    } else {
-        if (d1->dtype == PCV_BF16) pair1x1_kernel<PCV_BF16, 2><<<grid, 256, pair_lds(2), st>>>(p);
-        else pair1x1_kernel<PCV_F16, 2><<<grid, 256, pair_lds(2), st>>>(p);
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    const PairForm form = gate ? PAIR_GATED : (pb == 4 ? PAIR_PB4 : PAIR_PB2);
+    if (gate) p.nTiles = (int)((M + 31) / 32);          // the gated form is instantiated for PB == 2 only
+    const unsigned grid = (unsigned)std::min<long>(p.nTiles, (long)block_slots(ctx, ctx->pair_bpc[form == PAIR_PB4 ? 0 : 1]));
+    return launch(ctx, kPair[d1->dtype == PCV_BF16 ? 0 : 1][form], grid, st, p);
 }
 
 static const char* pair_idconv_unsupported(const pcv_conv_desc& di, const pcv_conv_desc& a, const pcv_conv_desc& b) {
     if (desc_stale(di)) return kStaleDesc;
     if (const char* why = pair_unsupported(a, b)) return why;
     if (a.Cin != 64) return "identity-convolution variant: only the 64 -> 256 -> 64 pair is instantiated";
-    const bool plain = di.kh == 1 && di.kw == 1 && di.stride_h == 1 && di.stride_w == 1 && di.pad_t == 0 && di.pad_l == 0 &&
-                       di.pad_b == 0 && di.pad_r == 0 && di.groups == 1 && di.dil_h == 1 && di.dil_w == 1 &&
-                       di.out_dtype == di.dtype && (di.x_cpitch == 0 || di.x_cpitch == di.Cin) &&
-                       (di.x_wpitch == 0 || di.x_wpitch == di.W) && (di.y_cpitch == 0 || di.y_cpitch == di.Cout);
-    if (!plain || di.dtype != a.dtype) return "identity convolution must be a plain 1x1 stride 1 of the same dtype";
+    if (!plain_1x1(di) || di.dtype != a.dtype) return "identity convolution must be a plain 1x1 stride 1 of the same dtype";
     if (di.N != a.N || di.H != a.H || di.W != a.W || di.Cin != 64 || di.Cout != a.Cout) return "identity convolution shapes do not match";
     if (di.act != PCV_ACT_NONE || di.has_residual || di.post_act != PCV_ACT_NONE) return "identity convolution must have no activation";
     return nullptr;
@@ -2215,12 +2086,8 @@ int pcv_conv1x1_pair_idconv_fused(pcv_ctx* ctx, const pcv_conv_desc* d_id, const
     p.w1_bytes = p.wid_bytes = 256 * 64 * 2; p.w2_bytes = 64 * 256 * 2;
     p.M = (int)M; p.nTiles = (int)((M + 31) / 32);
     p.act1 = d1->act; p.post1 = d1->post_act; p.act2 = d2->act;
-    const unsigned grid = (unsigned)std::min<long>(p.nTiles, (long)block_slots(ctx, g_pair_idc_blocks_per_cu));
-    hipStream_t st = (hipStream_t)stream;
-    if (d1->dtype == PCV_BF16) pair1x1_kernel<PCV_BF16, 2, true><<<grid, 256, pair_lds(2, true), st>>>(p);
-    else pair1x1_kernel<PCV_F16, 2, true><<<grid, 256, pair_lds(2, true), st>>>(p);
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    const unsigned grid = (unsigned)std::min<long>(p.nTiles, (long)block_slots(ctx, ctx->pair_idc_bpc));
+    return launch(ctx, kPair[d1->dtype == PCV_BF16 ? 0 : 1][PAIR_IDCONV], grid, (hipStream_t)stream, p);
 }
 
 int pcv_channel_slice(pcv_ctx* ctx, const void* x, void* y, long rows, int C, int offset, int x_cpitch, int y_cpitch, int dtype,
@@ -2363,7 +2230,7 @@ int pcv_mbconv_fused(pcv_ctx* ctx, const pcv_conv_desc* d_exp, const pcv_conv_de
     const bool block_shape = p.Cout <= 32 && p.Wo >= 24;
     // register-resident tiles (mbr.hpp): one expand K step, the unit's weights + diagonal fragments in LDS
     if (wave_shape && ctx->use_mbr) {
-        const MbrEntry* e = pick_mbr(d_dw->dtype, nrt, p.act_e == p.act_d ? p.act_e : -1, S, kaw, p.nChunks);
+        const MbrEntry* e = pick_mbr(ctx, d_dw->dtype, nrt, p.act_e == p.act_d ? p.act_e : -1, S, kaw, p.nChunks);
         if (e) {
             const int oc = mbr_out_cols(S, e->nrt);                             // output columns of a wave tile
             p.tilesH = (p.Ho + e->ro - 1) / e->ro; p.tilesW = (p.Wo + oc - 1) / oc;
@@ -2371,9 +2238,7 @@ int pcv_mbconv_fused(pcv_ctx* ctx, const pcv_conv_desc* d_exp, const pcv_conv_de
             if (nT >= 0x7FFFFFFFl) return fail(ctx, PCV_ERR_TOO_LARGE, "pcv_mbconv_fused: too many tiles; split the batch");
             p.nTiles = (int)nT;
             const unsigned gridr = (unsigned)std::min<long>((nT + e->waves - 1) / e->waves, (long)block_slots(ctx, 1));
-            hipLaunchKernelGGL(e->fn, dim3(gridr), dim3(64 * e->waves), mbr_entry_lds(*e, p.nChunks), (hipStream_t)stream, p);
-            HIP_TRY(ctx, hipGetLastError());
-            return PCV_OK;
+            return launch(ctx, mbr_kernel_of(*e, mbr_entry_lds(*e, p.nChunks)), gridr, (hipStream_t)stream, p);
         }
     }
     if (wave_shape && (ctx->use_mbw || !block_shape)) {
@@ -2393,22 +2258,17 @@ int pcv_mbconv_fused(pcv_ctx* ctx, const pcv_conv_desc* d_exp, const pcv_conv_de
             const MbwLds wl = mbw_lds_layout(S, nrt, p.nChunks, nw, tw, kaw, rbw);
             const long want = (nT + nw - 1) / nw;
             const unsigned gridw = (unsigned)std::min<long>(want, (long)block_slots(ctx, 1));
-            mbconv_fn fnw = pick_mbw(d_dw->dtype, S, nrt, p.act_e == p.act_d ? p.act_e : -1, tw, kaw, rbw);
-            if (!fnw) return fail(ctx, PCV_ERR_INVALID, "pcv_mbconv_fused: no kernel instantiation");
-            hipLaunchKernelGGL(fnw, dim3(gridw), dim3(64 * nw), wl.total, (hipStream_t)stream, p);
-            HIP_TRY(ctx, hipGetLastError());
-            return PCV_OK;
+            const MbwEntry* ew = pick_mbw(d_dw->dtype, S, nrt, p.act_e == p.act_d ? p.act_e : -1, tw, kaw, rbw);
+            if (!ew) return fail(ctx, PCV_ERR_INVALID, "pcv_mbconv_fused: no kernel instantiation");
+            return launch(ctx, mbw_kernel_of(*ew, nw, wl.total), gridw, (hipStream_t)stream, p);
         }
     }
     const MbLds lds = mbconv_plan(S, d_exp != nullptr, p.ka, p.nChunks, p.nRowT, &p.nbufX);
-    mbconv_fn fn = pick_mbconv(d_dw->dtype, S, d_exp != nullptr, p.nRowT);
-    int nb = 0;
-    HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(fn), 256, lds.total));
-    if (nb < 1) nb = 1;
+    const Kernel K = mbconv_kernel(d_dw->dtype, S, d_exp != nullptr, p.nRowT, lds.total);
+    int nb = 0;                 // (per launch: the resident blocks depend on the unit's LDS plan)
+    if (int rc = blocks_per_cu(ctx, K, &nb)) return rc;
     const unsigned grid = (unsigned)std::min<long>(p.nTiles, (long)block_slots(ctx, nb));
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(256), lds.total, (hipStream_t)stream, p);
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    return launch(ctx, K, grid, (hipStream_t)stream, p);
 }
 
 int pcv_bn_act(pcv_ctx* ctx, const void* x, const float* scale, const float* shift, void* y, long rows, int C, int x_cpitch,

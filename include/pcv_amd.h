@@ -181,7 +181,8 @@ int pcv_conv2d_nchw_stem_fused(pcv_ctx* ctx, const pcv_conv_desc* d, const float
 int pcv_dwconv2d_fused(pcv_ctx* ctx, const pcv_conv_desc* d, const void* x, const void* packed,
                        const float* scale, const float* shift, const void* residual, void* y, void* stream);
 /* nn.MaxPool2d(k, s, p, ceil_mode) of ResInitBlock (resnet.py:255-258, floor) and ShuffleInitBlock (shufflenetv2.py:111-115,
- * ceil_mode=True): -inf padding; with ceil_mode the last window may hang over the bottom / right edge (PyTorch's rule). */
+ * ceil_mode=True): -inf padding; with ceil_mode the last window may hang over the bottom / right edge (PyTorch's rule). A NaN
+ * in a window gives NaN, as in torch. y is [N, Ho, Wo, C] with PyTorch's output size; an empty one is PCV_ERR_INVALID. */
 int pcv_maxpool2d(pcv_ctx* ctx, const void* x, void* y, int N, int H, int W, int C, int k, int s, int p,
                   int ceil_mode, int dtype, void* stream);
 /* torch.chunk / channel slicing at ANY channel offset (shufflenetv2.py:80): y[rows, y_cpitch] gets x[.., offset .. offset+C),

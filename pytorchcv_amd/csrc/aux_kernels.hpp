@@ -168,7 +168,11 @@ __global__ __launch_bounds__(256) void bn_fold_kernel(int C, const float* gamma,
 }
 
 // ---- pooling ----------------------------------------------------------------------------------------------
-// nn.MaxPool2d(k, s, p) (resnet.py:255-258): -inf padding, floor output size.
+// nn.MaxPool2d(k, s, p, ceil_mode) (resnet.py:255-258): -inf padding; the host computes Ho / Wo (floor, or ceil with torch's rule
+// that the last window starts inside the map or its left padding). The reduction is gfx950's IEEE-754-2019 maximum
+// (one v_maximum3_f32 per tap and channel, as many instructions as the v_max_f32 it replaces), which PROPAGATES NaN like torch's max_pool2d and like the fused stem + pool (stem_conv.hpp
+// stem_pkmax): fmaxf (v_max3_f32) returns the non-NaN operand and would turn a NaN activation into an ordinary number, or into
+// -inf where the whole window is NaN (see ActClamp in pcv_common.hpp for why that must not happen).
 template <int DT>
 __global__ __launch_bounds__(256) void maxpool_kernel(const void* __restrict__ x, void* __restrict__ y, int N, int H, int W,
                                                      int C, int Ho, int Wo, int k, int s, int pad) {
@@ -194,7 +198,7 @@ __global__ __launch_bounds__(256) void maxpool_kernel(const void* __restrict__ x
             float v[8];
             load8<DT>(x, (((size_t)n * H + hi) * W + wi) * C + c0, v);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) m[e] = fmaxf(m[e], v[e]);
+            for (int e = 0; e < 8; ++e) m[e] = __builtin_elementwise_maximum(m[e], v[e]);
         }
     }
     store8<DT>(y, (size_t)i * 8, m);

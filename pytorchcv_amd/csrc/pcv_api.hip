@@ -1751,7 +1751,9 @@ int pcv_dwconv2d_fused(pcv_ctx* ctx, const pcv_conv_desc* d, const void* x, cons
 }
 
 static int pool_out(int in, int k, int s, int p, int ceil_mode) {
-    int o = ceil_mode ? (in + 2 * p - k + s - 1) / s + 1 : (in + 2 * p - k) / s + 1;
+    const int num = in + 2 * p - k + (ceil_mode ? s - 1 : 0);
+    if (num < 0) return 0;                                // torch divides rounding DOWN: empty (C's `/` would round -1 / 2 up to one row)
+    int o = num / s + 1;
     if (ceil_mode && (o - 1) * s >= in + p) --o;          // the last window must start inside the input or the left padding
     return o;
 }

@@ -667,6 +667,8 @@ def maxpool2d(x: NHWC, k: int, s: int, p: int, ceil_mode: bool = False) -> NHWC:
     if not x.dense:
         raise RuntimeError("max-pool on a padded handle")
     Ho, Wo = _pool_out(x.H, k, s, p, ceil_mode), _pool_out(x.W, k, s, p, ceil_mode)
+    if Ho <= 0 or Wo <= 0:
+        raise RuntimeError("MaxPool2d({}, {}, {}) output of a {}x{} map would be empty".format(k, s, p, x.H, x.W))
     y = torch.empty((x.N, Ho, Wo, x.cpitch), dtype=x.dtype, device=x.device)
     ctx = _ctx(x.device)
     _lib.check(_lib.lib().pcv_maxpool2d(ctx, _ptr(x.t), _ptr(y), x.N, x.H, x.W, x.cpitch, k, s, p, 1 if ceil_mode else 0,

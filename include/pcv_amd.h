@@ -32,7 +32,9 @@ extern "C" {
  * 3: + pcv_fp16_guard_begin / pcv_fp16_guard_end / pcv_fp16_overflow_count, + pcv_rccl_* (no layout change)
  * 4: no signature or struct change; the packed-weight blobs of 16-bit depthwise 3x3 layers and of the dense layers listed at
  *    pcv_conv_pack carry a second table, so a blob packed by a version-3 library is too short (size blobs with *_packed_bytes)
- * 5: + split attention (pcv_splat_squeeze / _excite / _combine) and padded average pool (pcv_avgpool2d_pad); no layout change */
+ * 5: + split attention (pcv_splat_squeeze / _excite / _combine) and padded average pool (pcv_avgpool2d_pad); no layout change
+ *    (still 5: + pcv_resize_plan_bytes / pcv_resize_plan / pcv_resize_crop_u8 - pure additions, no signature, struct or blob of
+ *    version 5 changes, so a version-5 binding keeps working against this library and the number does not move) */
 #define PCV_ABI_VERSION 5
 
 typedef struct pcv_ctx pcv_ctx;
@@ -123,6 +125,31 @@ int pcv_nhwc_to_nchw(pcv_ctx* ctx, const void* x, float* y, int N, int C, int H,
  * zero pad channels/columns - exactly what pcv_nchw_to_nhwc would produce from the fp32 NCHW tensor of the host pipeline. */
 int pcv_preprocess_u8(pcv_ctx* ctx, const unsigned char* x, void* y, int N, int Hs, int Ws, int C, int top, int left,
                       int H, int W, int wpitch, const float* mean, const float* inv_std, int dtype, void* stream);
+
+/* Decoded uint8 frames of ANY size - every frame of a batch its own [Hs_i, Ws_i, C] - to the same network input in ONE launch:
+ * torchvision's `Resize(size)` on a PIL image (the shorter side becomes `size`, the other int(size * long / short); PIL's antialiased
+ * bilinear `Image.resize`: two separable integer passes, horizontal first, 22-bit fixed-point coefficients, the intermediate rounded
+ * to uint8) + `CenterCrop(H x W)` + pcv_preprocess_u8's normalisation, layout and cast. This is the preprocessing the reference's
+ * published error rates were measured with (README.md:12-13, img_scale of model_metainfos.csv); its resize is an integer algorithm and
+ * is reproduced BIT FOR BIT: y equals pcv_preprocess_u8 applied to PIL's resized frames. Nothing in the reference's tree
+ * corresponds to it (its evaluation scripts live in imgclsmob). "Size it, pack it, run it", like the weights:
+ *   pcv_resize_plan_bytes  host arithmetic only (no context, no device): the size of the plan for frames of hs[i] x ws[i]. Refuses
+ *                          (PCV_ERR_INVALID, text in pcv_last_error(NULL)) N <= 0, a non-positive size / H / W, C outside 1..4, a crop
+ *                          larger than a resized frame, and a frame whose down-scale is so large that the source rows ONE output row
+ *                          reads cannot be staged on a CU (64 KB of H-resampled rows of W * C bytes: beyond about 48x at 224 x 3).
+ *   pcv_resize_plan        host only: fills `blob` (HOST memory, `bytes` = the answer above, anything else is refused) - a header
+ *                          (magic, N, C, H, W, total bytes), per frame its geometry (frames[i], the frame's DEVICE pointer; resized size,
+ *                          crop origin, source-row range, band height, table offsets) and the coefficient tables of the W crop
+ *                          columns and H crop rows only. Relocatable: copy it to the device like any packed weight.
+ *   pcv_resize_crop_u8     the launch. Launch geometry is read from `plan_host` (magic, `bytes` and every offset are validated before
+ *                          anything is launched), the kernel reads `plan_dev`, the caller's device copy of the same bytes (16-byte
+ *                          aligned). y is NHWC [N, H, wpitch, 4] in dtype, pad channel / pad columns zero, as pcv_preprocess_u8's.
+ * The frames and plan_dev are borrowed until the launch has run on `stream`. */
+int pcv_resize_plan_bytes(int N, const int* hs, const int* ws, int C, int size, int H, int W, size_t* bytes);
+int pcv_resize_plan(const void* const* frames, int N, const int* hs, const int* ws, int C, int size, int H, int W, void* blob,
+                    size_t bytes);
+int pcv_resize_crop_u8(pcv_ctx* ctx, const void* plan_host, const void* plan_dev, size_t bytes, void* y, int wpitch,
+                       const float* mean, const float* inv_std, int dtype, void* stream);
 
 /* ---- weights (load time) ------------------------------------------------------------------------------- */
 /* Size of the packed-weight blob of a dense or grouped conv (groups < Cin). */

@@ -514,6 +514,29 @@ __global__ __launch_bounds__(256) void bn_act_kernel(const void* __restrict__ x,
 // padded to 4 and the row pitch even, in the compute type; producing that directly from the decoded uint8 frames folds
 // crop + normalise + layout + cast into one read of 1 byte per element (instead of an fp32 NCHW tensor written by the host
 // pipeline and re-read by nchw_to_nhwc). One thread = one output pixel.
+//
+// The last stage, shared with resize_crop_u8_kernel (resize_kernel.hpp) so that both give the same bits from the same uint8 values:
+// one NHWC4 pixel at element offset `eoff` of y from the C <= 4 bytes of b (`inside` false: a pad column, zeros) - normalise,
+// fp16 range guard, cast, one 8- or 16-byte store.
+template <int OT>
+__device__ __forceinline__ void preprocess_store_px(const unsigned char (&b)[4], bool inside, int C, const float* __restrict__ mean,
+                                                    const float* __restrict__ inv_std, void* __restrict__ y, size_t eoff,
+                                                    uint32_t* __restrict__ ovf) {
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    if (inside) {
+        for (int c = 0; c < C && c < 4; ++c) v[c] = ((float)b[c] * (1.f / 255.f) - mean[c]) * inv_std[c];
+    }
+    F16Guard<OT> guard;
+    guard.see(v);
+    guard.commit(ovf);
+    if constexpr (OT == PCV_F32) {
+        *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(y) + eoff) = (f32x4){v[0], v[1], v[2], v[3]};
+    } else {
+        u32x2 o = {pack2<OT>(v[0], v[1]), pack2<OT>(v[2], v[3])};
+        *reinterpret_cast<u32x2*>(reinterpret_cast<uint16_t*>(y) + eoff) = o;
+    }
+}
+
 template <int OT>
 __global__ __launch_bounds__(256) void preprocess_u8_kernel(const unsigned char* __restrict__ x, void* __restrict__ y, int N,
                                                            int Hs, int Ws, int C, int top, int left, int H, int W, int cpitch,
@@ -525,21 +548,12 @@ __global__ __launch_bounds__(256) void preprocess_u8_kernel(const unsigned char*
     const long nh = pix / wpitch;
     const int h = (int)(nh % H);
     const int n = (int)(nh / H);
-    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    unsigned char b[4] = {0, 0, 0, 0};
     if (w < W) {
         const unsigned char* src = x + (((size_t)n * Hs + top + h) * Ws + left + w) * C;
-        for (int c = 0; c < C && c < 4; ++c) v[c] = ((float)src[c] * (1.f / 255.f) - mean[c]) * inv_std[c];
+        for (int c = 0; c < C && c < 4; ++c) b[c] = src[c];
     }
-    const size_t eoff = (size_t)pix * cpitch;
-    F16Guard<OT> guard;
-    guard.see(v);
-    guard.commit(ovf);
-    if constexpr (OT == PCV_F32) {
-        *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(y) + eoff) = (f32x4){v[0], v[1], v[2], v[3]};
-    } else {
-        u32x2 o = {pack2<OT>(v[0], v[1]), pack2<OT>(v[2], v[3])};
-        *reinterpret_cast<u32x2*>(reinterpret_cast<uint16_t*>(y) + eoff) = o;
-    }
+    preprocess_store_px<OT>(b, w < W, C, mean, inv_std, y, (size_t)pix * cpitch, ovf);
 }
 
 // ---- channel plumbing of ShuffleNet-style units (shufflenetv2.py:69-91; common/tutti.py:267-291) ---------------------------------

@@ -35,6 +35,7 @@ MBR_SHAPES(MBR_DECLARE, PCV_BF16)
 MBR_SHAPES(MBR_DECLARE, PCV_F16)
 #include "dwconv.hpp"
 #include "aux_kernels.hpp"
+#include "resize_kernel.hpp"
 #include "head_gemm.hpp"
 
 
@@ -2171,6 +2172,46 @@ int pcv_preprocess_u8(pcv_ctx* ctx, const unsigned char* x, void* y, int N, int 
     if (dtype == PCV_BF16) preprocess_u8_kernel<PCV_BF16><<<grid, 256, 0, st>>>(x, y, N, Hs, Ws, C, top, left, H, W, 4, wpitch, mean, inv_std, ctx->ovf);
     else if (dtype == PCV_F16) preprocess_u8_kernel<PCV_F16><<<grid, 256, 0, st>>>(x, y, N, Hs, Ws, C, top, left, H, W, 4, wpitch, mean, inv_std, ctx->ovf);
     else preprocess_u8_kernel<PCV_F32><<<grid, 256, 0, st>>>(x, y, N, Hs, Ws, C, top, left, H, W, 4, wpitch, mean, inv_std, ctx->ovf);
+    HIP_TRY(ctx, hipGetLastError());
+    return PCV_OK;
+}
+
+// Resize + crop + normalise of ragged frames (resize_plan.hpp, resize_kernel.hpp). The two planning calls are host arithmetic only:
+// no context, no device; their refusals leave the text where pcv_last_error(NULL) finds it.
+int pcv_resize_plan_bytes(int N, const int* hs, const int* ws, int C, int size, int H, int W, size_t* bytes) {
+    if (!bytes) return fail(nullptr, PCV_ERR_INVALID, "pcv_resize_plan_bytes: bytes is NULL");
+    *bytes = 0;
+    if (const char* why = pcv_resize::plan_bytes(N, hs, ws, C, size, H, W, bytes))
+        return fail(nullptr, PCV_ERR_INVALID, std::string("pcv_resize_plan_bytes: ") + why);
+    return PCV_OK;
+}
+
+int pcv_resize_plan(const void* const* frames, int N, const int* hs, const int* ws, int C, int size, int H, int W, void* blob,
+                    size_t bytes) {
+    if (const char* why = pcv_resize::plan(frames, N, hs, ws, C, size, H, W, blob, bytes))
+        return fail(nullptr, PCV_ERR_INVALID, std::string("pcv_resize_plan: ") + why);
+    return PCV_OK;
+}
+
+int pcv_resize_crop_u8(pcv_ctx* ctx, const void* plan_host, const void* plan_dev, size_t bytes, void* y, int wpitch,
+                       const float* mean, const float* inv_std, int dtype, void* stream) {
+    if (!ctx) return PCV_ERR_INVALID;
+    DeviceGuard device_guard(ctx->device);
+    if (!plan_host || !plan_dev || !y || !mean || !inv_std || !dtype_ok(dtype) || !aligned16(plan_dev) || !aligned16(y))
+        return fail(ctx, PCV_ERR_INVALID, "pcv_resize_crop_u8: bad argument (NULL pointer, dtype, or plan_dev / y not 16-byte aligned)");
+    if (const char* why = pcv_resize::validate(plan_host, bytes)) return fail(ctx, PCV_ERR_INVALID, std::string("pcv_resize_crop_u8: ") + why);
+    pcv_resize::ResizeHeader hd;
+    std::memcpy(&hd, plan_host, sizeof(hd));
+    if (wpitch < hd.W) return fail(ctx, PCV_ERR_INVALID, "pcv_resize_crop_u8: wpitch < W");
+    if (!in_window((unsigned long long)hd.N * hd.H * wpitch * 4 * esize(dtype))) return too_large(ctx, "pcv_resize_crop_u8", "y");
+    int blocks = hd.items;                                                  // a fresh block per (frame, band): see resize_kernel.hpp
+    if (ctx->max_blocks > 0 && blocks > ctx->max_blocks) blocks = ctx->max_blocks;      // multi-round tests only (as pcv_se_scale)
+    const char* pd = static_cast<const char*>(plan_dev);
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned lds = (unsigned)hd.stage_bytes;
+    if (dtype == PCV_BF16) resize_crop_u8_kernel<PCV_BF16><<<blocks, 256, lds, st>>>(pd, y, wpitch, mean, inv_std, ctx->ovf);
+    else if (dtype == PCV_F16) resize_crop_u8_kernel<PCV_F16><<<blocks, 256, lds, st>>>(pd, y, wpitch, mean, inv_std, ctx->ovf);
+    else resize_crop_u8_kernel<PCV_F32><<<blocks, 256, lds, st>>>(pd, y, wpitch, mean, inv_std, ctx->ovf);
     HIP_TRY(ctx, hipGetLastError());
     return PCV_OK;
 }

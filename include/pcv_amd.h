@@ -34,7 +34,8 @@ extern "C" {
  *    pcv_conv_pack carry a second table, so a blob packed by a version-3 library is too short (size blobs with *_packed_bytes)
  * 5: + split attention (pcv_splat_squeeze / _excite / _combine) and padded average pool (pcv_avgpool2d_pad); no layout change
  *    (still 5: + pcv_resize_plan_bytes / pcv_resize_plan / pcv_resize_crop_u8 - pure additions, no signature, struct or blob of
- *    version 5 changes, so a version-5 binding keeps working against this library and the number does not move) */
+ *    version 5 changes, so a version-5 binding keeps working against this library and the number does not move;
+ *    likewise + pcv_classify_f32) */
 #define PCV_ABI_VERSION 5
 
 typedef struct pcv_ctx pcv_ctx;
@@ -150,6 +151,24 @@ int pcv_resize_plan(const void* const* frames, int N, const int* hs, const int* 
                     size_t bytes);
 int pcv_resize_crop_u8(pcv_ctx* ctx, const void* plan_host, const void* plan_dev, size_t bytes, void* y, int wpitch,
                        const float* mean, const float* inv_std, int dtype, void* stream);
+
+/* ---- after the logits: top-k, softmax, label rank -------------------------------------------------------- */
+/* logits: contiguous fp32 [N, J], what every net's classifier writes. The reference keeps this step out of tree (the imgclsmob
+ * scripts, torch.topk); it is what produced the Top1 / Top5 columns of the reference README and of models/common/model_metainfos.csv.
+ * ONE total order "a precedes b" defines every output: NaN is above +inf; otherwise the larger value comes first; equal values are
+ * ordered by lower index first; all NaNs tie with each other and -0.0 ties with +0.0 (torch.topk leaves ties unspecified).
+ *   top_idx, top_val [N, k]  the first k entries of a row in that order; top_val carries the input's bits unchanged
+ *   top_prob [N, k]          their softmax probability: maximum and sum of expf(x - max) over the whole row, in fp32
+ *   rank [N]                 how many entries precede (x[label], label): exact for every k at once, top-k error = count(rank >= k)
+ *   nll [N]                  log(sum) + max - x[label]
+ * Any output may be NULL; rank / nll need labels; k = 0 is allowed when the three top_* are NULL. A label outside [0, J) gives
+ * rank = J and nll = +inf. Rows with a NaN, a +inf or only -inf are not special-cased: their probabilities and nll are NaN, as
+ * torch.softmax's are. Limits (PCV_ERR_INVALID beyond them): N >= 1, 1 <= J <= 16384, 0 <= k <= min(J, 32). One workgroup per row,
+ * fixed reduction order, no atomics: a row's outputs are bit-identical wherever the row sits in the batch. */
+int pcv_classify_f32(pcv_ctx* ctx, const float* logits, int N, int J, int k,
+                     int* top_idx, float* top_val, float* top_prob,
+                     const long long* labels, int* rank, float* nll,
+                     void* stream);
 
 /* ---- weights (load time) ------------------------------------------------------------------------------- */
 /* Size of the packed-weight blob of a dense or grouped conv (groups < Cin). */

@@ -60,6 +60,7 @@ _SIGS = {
     "pcv_resize_plan_bytes": (_I, [_I, ctypes.POINTER(_I), ctypes.POINTER(_I), _I, _I, _I, _I, ctypes.POINTER(ctypes.c_size_t)]),
     "pcv_resize_plan": (_I, [ctypes.POINTER(_VP), _I, ctypes.POINTER(_I), ctypes.POINTER(_I), _I, _I, _I, _I, _VP, ctypes.c_size_t]),
     "pcv_resize_crop_u8": (_I, [_VP, _VP, _VP, ctypes.c_size_t, _VP, _I, _VP, _VP, _I, _VP]),
+    "pcv_classify_f32": (_I, [_VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "pcv_conv_packed_bytes": (_I, [ctypes.POINTER(ConvDesc), ctypes.POINTER(ctypes.c_size_t)]),
     "pcv_conv_pack": (_I, [_VP, ctypes.POINTER(ConvDesc), _VP, _VP, _VP]),
     "pcv_dwconv_packed_bytes": (_I, [ctypes.POINTER(ConvDesc), ctypes.POINTER(ctypes.c_size_t)]),

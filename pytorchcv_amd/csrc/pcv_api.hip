@@ -36,6 +36,7 @@ MBR_SHAPES(MBR_DECLARE, PCV_F16)
 #include "dwconv.hpp"
 #include "aux_kernels.hpp"
 #include "resize_kernel.hpp"
+#include "classify_kernel.hpp"
 #include "head_gemm.hpp"
 
 
@@ -666,6 +667,12 @@ static MbLds mbconv_plan(int stride, bool expand, int ka, int nChunks, int nRowT
     return two;
 }
 
+// top-k / softmax / label rank (classify_kernel.hpp): one wave per row up to 1024 entries, four above; LDS = scratch + the row
+static Kernel classify_kernel_of(int J) {
+    const int lds = kClassifyRedBytes + J * 4;
+    return J <= 1024 ? kernel_of(classify_kernel<64>, 64, lds) : kernel_of(classify_kernel<256>, 256, lds);
+}
+
 // ---- once per context: every instantiation with dynamic LDS gets its limit raised on the context's device, and the persistent
 // kernels whose grid is a number of resident blocks get that number recorded in the context ---------------------------------------
 static int enable_kernel(pcv_ctx* ctx, const Kernel& k, int* bpc) {
@@ -726,6 +733,8 @@ static int enable_kernels(pcv_ctx* ctx) {
                 for (int rt = 2; rt <= 6; rt += 4) on(mbconv_kernel(dt, s, e != 0, rt));
     for (const MbwEntry& e : kMbw) on(mbw_kernel_of(e));
     for (const MbrEntry& e : kMbr) on(mbr_kernel_of(e));
+    on(classify_kernel_of(1024));
+    on(classify_kernel_of(kClassifyMaxJ));
     return rc;
 }
 // Shapes the wave-private kernel (mbw.hpp) runs: an expand convolution with one K step (Cin <= 32: any stride, <= 64 projected
@@ -2213,6 +2222,27 @@ int pcv_resize_crop_u8(pcv_ctx* ctx, const void* plan_host, const void* plan_dev
     else if (dtype == PCV_F16) resize_crop_u8_kernel<PCV_F16><<<blocks, 256, lds, st>>>(pd, y, wpitch, mean, inv_std, ctx->ovf);
     else resize_crop_u8_kernel<PCV_F32><<<blocks, 256, lds, st>>>(pd, y, wpitch, mean, inv_std, ctx->ovf);
     HIP_TRY(ctx, hipGetLastError());
+    return PCV_OK;
+}
+
+int pcv_classify_f32(pcv_ctx* ctx, const float* logits, int N, int J, int k, int* top_idx, float* top_val, float* top_prob,
+                     const long long* labels, int* rank, float* nll, void* stream) {
+    if (!ctx) return PCV_ERR_INVALID;
+    DeviceGuard device_guard(ctx->device);
+    if (!logits) return fail(ctx, PCV_ERR_INVALID, "pcv_classify_f32: logits is NULL");
+    if (N < 1) return fail(ctx, PCV_ERR_INVALID, "pcv_classify_f32: N = " + std::to_string(N) + " is outside the limit N >= 1");
+    if (J < 1 || J > kClassifyMaxJ)
+        return fail(ctx, PCV_ERR_INVALID, "pcv_classify_f32: J = " + std::to_string(J) + " is outside the limit 1 <= J <= 16384 (a row is staged in 64 KB of LDS)");
+    if (k < 0 || k > std::min(J, kClassifyMaxK))
+        return fail(ctx, PCV_ERR_INVALID, "pcv_classify_f32: k = " + std::to_string(k) + " is outside the limit 0 <= k <= min(J, 32) (J = " + std::to_string(J) + ")");
+    if (k == 0 && (top_idx || top_val || top_prob))
+        return fail(ctx, PCV_ERR_INVALID, "pcv_classify_f32: k = 0 is allowed only when top_idx, top_val and top_prob are all NULL");
+    if ((rank || nll) && !labels) return fail(ctx, PCV_ERR_INVALID, "pcv_classify_f32: rank and nll need labels");
+    long long blocks = N;
+    if (ctx->max_blocks > 0 && blocks > ctx->max_blocks) blocks = ctx->max_blocks;      // multi-round tests only (as pcv_se_scale)
+    const Kernel K = classify_kernel_of(J);
+    void* args[] = {&logits, &N, &J, &k, &top_idx, &top_val, &top_prob, &labels, &rank, &nll};
+    HIP_TRY(ctx, hipLaunchKernel(K.fn, dim3((unsigned)blocks), dim3((unsigned)K.threads), args, (size_t)K.lds, (hipStream_t)stream));
     return PCV_OK;
 }
 

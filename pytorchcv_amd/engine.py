@@ -6,7 +6,7 @@
 
 __all__ = ['NHWC', 'DTYPES', 'default_dtype', 'set_compute_dtype', 'compute_dtype_of', 'Fp16Guard', 'fp16_overflow_count', 'from_nchw', 'to_nchw', 'ConvRunner',
            'BnActRunner', 'maxpool2d', 'avgpool2d', 'avgpool2d_pad', 'global_avgpool', 'se_forward', 'splat_forward', 'channel_slice', 'cat_shuffle2', 'act_code',
-           'boundary', 'round8', 'channel_concat_into', 'interpolate', 'add']
+           'boundary', 'round8', 'channel_concat_into', 'interpolate', 'add', 'classify']
 
 import os
 import ctypes
@@ -901,3 +901,38 @@ def splat_forward(x: NHWC, radix: int, groups: int, w1, b1, w2, b2, residual: NH
     _lib.check(L.pcv_splat_combine(ctx, _ptr(x.t), _ptr(att), _ptr(residual.t) if residual is not None else None, _ptr(y), N, HW,
                                    C, radix, post_act, code, st), ctx)
     return NHWC(y, N, x.H, x.W, C)
+
+
+def classify(logits: torch.Tensor, k: int = 0, labels=None, probs: bool = False, nll: bool = False) -> dict:
+    """What follows the logits, one launch (pcv_classify_f32) on the current stream: for fp32 logits [N, J] a dict of device tensors -
+    "ids" (int32 [N, k]) and "values" (fp32 [N, k]) when k > 0, "probs" (fp32 [N, k], softmax over the whole row) with `probs`,
+    "rank" (int32 [N]) when `labels` are given, "nll" (fp32 [N]) with `nll`. The order: NaN above +inf, larger first, equal values by
+    lower index, -0 ties with +0; "rank" counts the entries that precede the label, so top-k error for any k is count(rank >= k).
+    Labels of any integer dtype, converted to int64 on the device; one outside [0, J) gives rank J and nll +inf. The limits
+    (J <= 16384, k <= min(J, 32), nll needs labels) are the library's: it refuses with PcvError."""
+    if not torch.is_tensor(logits) or logits.dim() != 2 or logits.dtype != torch.float32:
+        raise TypeError("expected fp32 logits [N, J]")
+    dev = logits.device
+    ctx = _ctx(dev)
+    logits = logits.contiguous()
+    N, J = int(logits.shape[0]), int(logits.shape[1])
+    k = int(k)
+    out = {}
+    if k > 0:
+        out["ids"] = torch.empty((N, k), dtype=torch.int32, device=dev)
+        out["values"] = torch.empty((N, k), dtype=torch.float32, device=dev)
+    if probs:
+        out["probs"] = torch.empty((N, max(k, 0)), dtype=torch.float32, device=dev)
+    if labels is not None:
+        if not torch.is_tensor(labels) or labels.is_floating_point() or labels.is_complex() or labels.dtype == torch.bool:
+            raise TypeError("labels must be a tensor of an integer dtype")
+        if labels.numel() != N:
+            raise ValueError("expected {} labels, got {}".format(N, labels.numel()))
+        labels = labels.reshape(N).to(device=dev, dtype=torch.int64).contiguous()
+        out["rank"] = torch.empty((N,), dtype=torch.int32, device=dev)
+    if nll:
+        out["nll"] = torch.empty((N,), dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().pcv_classify_f32(ctx, _ptr(logits), N, J, k, _ptr(out.get("ids")), _ptr(out.get("values")),
+                                           _ptr(out.get("probs")), _ptr(labels), _ptr(out.get("rank")), _ptr(out.get("nll")),
+                                           _stream(dev)), ctx)
+    return out

@@ -8,6 +8,15 @@
 __all__ = ['GraphedNet', 'PipelinedNet', 'capture', 'capture_best', 'auto_lanes']
 
 import torch
+from .engine import NHWC
+
+
+def _is_handle(x) -> bool:
+    return isinstance(x, NHWC)
+
+
+def _copy_handle(h: NHWC) -> NHWC:
+    return NHWC(h.t.detach().clone(), h.N, h.H, h.W, h.C, wpitch=h.wpitch, cpitch=h.cpitch)
 
 
 class GraphedNet(object):
@@ -15,23 +24,30 @@ class GraphedNet(object):
     g = GraphedNet(net, example)      # example: fp32 NCHW tensor on the MI355X, defines the captured shape
     y = g(x)                          # x is copied into the static input; y is the graph's static output buffer
                                       # (valid until the next call; pass clone=True for an owned copy)
+    `example` may also be an `engine.NHWC` input handle (what `eval.preprocess_u8` / `preprocess_frames` return): the handle's tensor
+    IS the static input - the caller refills it in place (`preprocess_*(..., out=g.static_in)`) and calls `g(None)`. One lane only.
     """
     def __init__(self, net: torch.nn.Module, example: torch.Tensor, warmup: int = 2, own_input: bool = False,
                  lanes: int | None = None):
         if example.device.type != "cuda":
             raise RuntimeError("graph capture needs the example input on the MI355X")
         self.net = net
+        if _is_handle(example) and lanes not in (None, 1):
+            raise ValueError("an input handle is captured with lanes=1 (got lanes={}): batch lanes slice an NCHW tensor".format(lanes))
         # lanes > 1: the batch is cut into `lanes` slices whose forwards are independent branches of the graph. The persistent
         # convolution kernels of one slice leave block slots idle in the last partial round of their tile schedule; the other
         # branch's kernels take those slots, so the tails overlap instead of adding up (DESIGN.md section 6).
         # Measured (bench.py --lanes, one MI355X, bf16): +4 .. +12 % images/s at batch 128-512 on every benchmarked net with two
         # lanes, three no better, neutral below batch 64 -> `lanes=None` picks 2 from batch 64 up.
         if lanes is None:
-            lanes = auto_lanes(example.shape[0])
-        self.lanes = max(1, min(int(lanes), example.shape[0]))
+            lanes = 1 if _is_handle(example) else auto_lanes(example.shape[0])
+        self.lanes = 1 if _is_handle(example) else max(1, min(int(lanes), example.shape[0]))
         self._side = [torch.cuda.Stream(device=example.device) for _ in range(self.lanes - 1)]
         # own_input: `example` itself becomes the static input buffer (the caller refills it in place; no copy per call)
-        self.static_in = example if (own_input and example.is_contiguous()) else example.detach().clone().contiguous()
+        if _is_handle(example):
+            self.static_in = example
+        else:
+            self.static_in = example if (own_input and example.is_contiguous()) else example.detach().clone().contiguous()
         dev = self.static_in.device
         with torch.no_grad():
             # side stream warm-up (weight packing, allocator warm-up) as torch's capture rules require
@@ -66,6 +82,8 @@ class GraphedNet(object):
     def __call__(self, x: torch.Tensor | None, clone: bool = False) -> torch.Tensor:
         """`x = None`: replay on whatever the static input holds (the caller filled it in place)."""
         if x is not None:
+            if _is_handle(self.static_in):
+                raise RuntimeError("captured on an input handle: refill `static_in` in place and call with None")
             if x.shape != self.static_in.shape:
                 raise RuntimeError("captured for input shape {}, got {}".format(tuple(self.static_in.shape), tuple(x.shape)))
             if x.data_ptr() != self.static_in.data_ptr():
@@ -90,6 +108,8 @@ class PipelinedNet(object):
     def __init__(self, net: torch.nn.Module, example: torch.Tensor, depth: int = 2, lanes: int = 1, own_input: bool = False):
         if example.device.type != "cuda":
             raise RuntimeError("graph capture needs the example input on the MI355X")
+        if _is_handle(example) and int(lanes) != 1:
+            raise ValueError("an input handle is captured with lanes=1 (got lanes={}): batch lanes slice an NCHW tensor".format(lanes))
         self.depth, self.lanes = max(1, int(depth)), max(1, int(lanes))
         dev = example.device
         self._dev = dev
@@ -99,7 +119,10 @@ class PipelinedNet(object):
         for i, st in enumerate(self._streams):
             st.wait_stream(cur)
             with torch.cuda.stream(st):
-                ex = example if (i == 0 and own_input) else example.detach().clone()
+                if _is_handle(example):
+                    ex = _copy_handle(example)                       # every slot its own handle; the caller's stays the caller's
+                else:
+                    ex = example if (i == 0 and own_input) else example.detach().clone()
                 self._slots.append(GraphedNet(net, ex, own_input=True, lanes=self.lanes))
         torch.cuda.synchronize(dev)
         self._next = 0
@@ -112,14 +135,19 @@ class PipelinedNet(object):
     def next_slot(self):
         return self._next
 
-    def __call__(self, x: torch.Tensor | None = None, then=None):
+    def __call__(self, x: torch.Tensor | None = None, then=None, fill=None):
         """Enqueue one step (x = None: the slot's static input as the caller left it). `then(y)`, if given, is issued on the slot's
-        stream right behind the replay (a collective on the logits, a copy-out) and its result is returned instead of y."""
+        stream right behind the replay (a collective on the logits, a copy-out) and its result is returned instead of y.
+        `fill(static_input)`, if given, is issued on the slot's stream right BEFORE the replay and writes the slot's input in place
+        (`preprocess_*(..., out=static_input)`). Everything that touches a slot's buffers is then ordered on that slot's stream:
+        refilling a slot from the caller's stream while its previous replay still reads the input would be a write-after-read race."""
         k = self._next
         self._next = (k + 1) % self.depth
         g, st = self._slots[k], self._streams[k]
         st.wait_stream(torch.cuda.current_stream(self._dev))         # x (if any) was produced on the caller's stream
         with torch.cuda.stream(st):
+            if fill is not None:
+                fill(g.static_in)
             y = g(x)
             if then is not None:
                 y = then(y)

@@ -35,7 +35,7 @@ extern "C" {
  * 5: + split attention (pcv_splat_squeeze / _excite / _combine) and padded average pool (pcv_avgpool2d_pad); no layout change
  *    (still 5: + pcv_resize_plan_bytes / pcv_resize_plan / pcv_resize_crop_u8 - pure additions, no signature, struct or blob of
  *    version 5 changes, so a version-5 binding keeps working against this library and the number does not move;
- *    likewise + pcv_classify_f32) */
+ *    likewise + pcv_classify_f32, + pcv_cbam_pool / _excite / _spatial_pool / _apply) */
 #define PCV_ABI_VERSION 5
 
 typedef struct pcv_ctx pcv_ctx;
@@ -292,6 +292,29 @@ int pcv_splat_combine(pcv_ctx* ctx, const void* x, const float* att, const void*
  * are pcv_avgpool2d's. */
 int pcv_avgpool2d_pad(pcv_ctx* ctx, const void* x, void* y, int N, int H, int W, int C, int k, int s, int p, int ceil_mode,
                       int count_include_pad, int dtype, int out_dtype, void* stream);
+
+/* CBAM block (cbamresnet.py:105-128: ChannelGate, then SpatialGate) on the NHWC output x [N, HW, C] of a unit body, four launches,
+ * fp32 between them; the channel-gated tensor is never written - x is read three times and y written once:
+ *   pool          s[N][2][C]: s[n][0] = mean_HW x, s[n][1] = max_HW x (AdaptiveAvgPool2d / AdaptiveMaxPool2d, cbamresnet.py:64-65,
+ *                 72, 74); one read of x, fixed order per image; the mean has pcv_se_squeeze's bits, the max propagates NaN.
+ *   excite        gate[N][C] = sigmoid(fc2(relu(fc1(mean))) + fc2(relu(fc1(max)))) (ChannelGate.forward, cbamresnet.py:71-77; MLP,
+ *                 :40-45); w1 fp32 [M, C], b1 [M], w2 fp32 [C, M], b2 [C]; `mid` is caller-provided fp32 storage [N][2][M].
+ *                 An image's gate does not depend on its position in the batch.
+ *   spatial_pool  p[N][HW][2]: p[..][0] = max_c (x * gate), p[..][1] = mean_c (x * gate) (SpatialGate.forward, cbamresnet.py:96-98:
+ *                 the `cat` puts the max first); the product is formed in fp32 registers; the max propagates NaN.
+ *   apply         sg[n,h,w] = sigmoid(scale[0] * conv7x7(p, w7, pad 3) + shift[0]) (cbamresnet.py:89-92,99-100: w7 fp32 [2][7][7],
+ *                 scale / shift: one device float each, the folded BatchNorm of the 1-channel convolution);
+ *                 y = post_act((x * gate[n,c]) * sg[n,h,w] + residual) (cbamresnet.py:79,101 and the unit's `x + identity`, ReLU,
+ *                 :181-182), the reference's multiplication order, one rounding, fp16 range-guarded; residual may be NULL.
+ * C % 8 == 0, C >= 8, M >= 1, N, H, W >= 1, required pointers non-NULL, known dtype / activation codes; anything else is
+ * PCV_ERR_INVALID. No host synchronisation, no allocation: capturable. */
+int pcv_cbam_pool(pcv_ctx* ctx, const void* x, float* s, int N, int HW, int C, int dtype, void* stream);
+int pcv_cbam_excite(pcv_ctx* ctx, const float* s, const float* w1, const float* b1, const float* w2, const float* b2, float* mid,
+                    float* gate, int N, int C, int M, void* stream);
+int pcv_cbam_spatial_pool(pcv_ctx* ctx, const void* x, const float* gate, float* p, int N, int HW, int C, int dtype, void* stream);
+int pcv_cbam_apply(pcv_ctx* ctx, const void* x, const float* gate, const float* p, const float* w7, const float* scale,
+                   const float* shift, const void* residual, void* y, int N, int H, int W, int C, int post_act, int dtype,
+                   void* stream);
 
 /* Two chained 1x1 ConvBlocks in one launch: y1 = post_act1(act1(conv1(x)*s1+b1) + residual) - the last convolution of a
  * bottleneck unit with its skip add (resnet.py:227-228) - and y2 = act2(conv2(y1)*s2+b2), the first convolution of the NEXT

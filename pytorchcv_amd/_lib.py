@@ -102,6 +102,10 @@ _SIGS = {
     "pcv_splat_excite": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _VP]),
     "pcv_splat_combine": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP]),
     "pcv_avgpool2d_pad": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _VP]),
+    "pcv_cbam_pool": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP]),
+    "pcv_cbam_excite": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP]),
+    "pcv_cbam_spatial_pool": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP]),
+    "pcv_cbam_apply": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP]),
 }
 
 _lib = None

@@ -35,6 +35,7 @@ MBR_SHAPES(MBR_DECLARE, PCV_BF16)
 MBR_SHAPES(MBR_DECLARE, PCV_F16)
 #include "dwconv.hpp"
 #include "aux_kernels.hpp"
+#include "cbam_kernels.hpp"
 #include "resize_kernel.hpp"
 #include "classify_kernel.hpp"
 #include "head_gemm.hpp"
@@ -1937,6 +1938,101 @@ int pcv_splat_combine(pcv_ctx* ctx, const void* x, const float* att, const void*
     else if (dtype == PCV_F16)
         splat_combine_kernel<PCV_F16><<<(unsigned)blocks, 256, 0, st>>>(x, att, residual, y, total8, HW, C, radix, post_act, ctx->ovf);
     else splat_combine_kernel<PCV_F32><<<(unsigned)blocks, 256, 0, st>>>(x, att, residual, y, total8, HW, C, radix, post_act, ctx->ovf);
+    HIP_TRY(ctx, hipGetLastError());
+    return PCV_OK;
+}
+
+// ---- CBAM (cbamresnet.py:48-128): four launches, no tensor of x's size written but y (cbam_kernels.hpp). Like the other aux kernels
+// they use static LDS only and are launched directly: nothing to enable, no occupancy slot in the context. -----------------------------
+static inline bool cbam_shape_ok(int N, long HW, int C) { return N > 0 && HW > 0 && C >= 8 && C % 8 == 0; }
+
+int pcv_cbam_pool(pcv_ctx* ctx, const void* x, float* s, int N, int HW, int C, int dtype, void* stream) {
+    if (!ctx) return PCV_ERR_INVALID;
+    DeviceGuard device_guard(ctx->device);
+    if (!x || !s || !cbam_shape_ok(N, HW, C) || !dtype_ok(dtype))
+        return fail(ctx, PCV_ERR_INVALID, "pcv_cbam_pool: bad argument (C must be a multiple of 8)");
+    hipStream_t st = (hipStream_t)stream;
+    dim3 grid((unsigned)N, (unsigned)((C / 8 + 511) / 512));
+    if (dtype == PCV_BF16) cbam_pool_kernel<PCV_BF16><<<grid, 512, 0, st>>>(x, s, HW, C);
+    else if (dtype == PCV_F16) cbam_pool_kernel<PCV_F16><<<grid, 512, 0, st>>>(x, s, HW, C);
+    else cbam_pool_kernel<PCV_F32><<<grid, 512, 0, st>>>(x, s, HW, C);
+    HIP_TRY(ctx, hipGetLastError());
+    return PCV_OK;
+}
+
+int pcv_cbam_excite(pcv_ctx* ctx, const float* s, const float* w1, const float* b1, const float* w2, const float* b2, float* mid,
+                    float* gate, int N, int C, int M, void* stream) {
+    if (!ctx) return PCV_ERR_INVALID;
+    DeviceGuard device_guard(ctx->device);
+    if (!s || !w1 || !b1 || !w2 || !b2 || !mid || !gate || !cbam_shape_ok(N, 1, C) || M < 1 || N > (1 << 30))
+        return fail(ctx, PCV_ERR_INVALID, "pcv_cbam_excite: bad argument (C must be a multiple of 8, M >= 1)");
+    if ((N + 7) / 8 > 65535) return too_large(ctx, "pcv_cbam_excite", "the batch");
+    hipStream_t st = (hipStream_t)stream;
+    launch_se_fc(s, w1, b1, mid, 2 * N, C, M, PCV_ACT_RELU, st);          // the mean row and the max row of every image: s is [2N][C]
+    dim3 grid((unsigned)((C + 255) / 256), (unsigned)((N + 7) / 8));
+    cbam_gate_kernel<<<grid, 256, 0, st>>>(mid, w2, b2, gate, N, C, M);
+    HIP_TRY(ctx, hipGetLastError());
+    return PCV_OK;
+}
+
+int pcv_cbam_spatial_pool(pcv_ctx* ctx, const void* x, const float* gate, float* p, int N, int HW, int C, int dtype, void* stream) {
+    if (!ctx) return PCV_ERR_INVALID;
+    DeviceGuard device_guard(ctx->device);
+    if (!x || !gate || !p || !cbam_shape_ok(N, HW, C) || !dtype_ok(dtype))
+        return fail(ctx, PCV_ERR_INVALID, "pcv_cbam_spatial_pool: bad argument (C must be a multiple of 8)");
+    int LP = 1;
+    while (LP < 64 && LP < C / 8) LP *= 2;                              // lanes of a pixel: min(64, C / 8), as a power of two
+    const int slots = 256 / LP;
+    // about 16 K elements per block (the gate staging is paid once per block), a whole number of rounds of the block's pixel slots
+    int ppb = std::max(slots, 16384 / C);
+    ppb = (ppb + slots - 1) / slots * slots;
+    const int bpi = (HW + ppb - 1) / ppb;
+    const long long blocks = (long long)N * bpi;
+    if (blocks > 0x7fffffffll) return too_large(ctx, "pcv_cbam_spatial_pool", "the grid");
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == PCV_BF16) cbam_spatial_pool_kernel<PCV_BF16><<<(unsigned)blocks, 256, 0, st>>>(x, gate, p, HW, C, LP, ppb, bpi);
+    else if (dtype == PCV_F16) cbam_spatial_pool_kernel<PCV_F16><<<(unsigned)blocks, 256, 0, st>>>(x, gate, p, HW, C, LP, ppb, bpi);
+    else cbam_spatial_pool_kernel<PCV_F32><<<(unsigned)blocks, 256, 0, st>>>(x, gate, p, HW, C, LP, ppb, bpi);
+    HIP_TRY(ctx, hipGetLastError());
+    return PCV_OK;
+}
+
+int pcv_cbam_apply(pcv_ctx* ctx, const void* x, const float* gate, const float* p, const float* w7, const float* scale, const float* shift,
+                   const void* residual, void* y, int N, int H, int W, int C, int post_act, int dtype, void* stream) {
+    if (!ctx) return PCV_ERR_INVALID;
+    DeviceGuard device_guard(ctx->device);
+    if (!x || !gate || !p || !w7 || !scale || !shift || !y || N <= 0 || H <= 0 || W <= 0 || C < 8 || C % 8 != 0 || !dtype_ok(dtype) ||
+        post_act < PCV_ACT_NONE || post_act > PCV_ACT_HSWISH)
+        return fail(ctx, PCV_ERR_INVALID, "pcv_cbam_apply: bad argument (C must be a multiple of 8)");
+    if ((long long)H * W > 0x7fffffffll) return too_large(ctx, "pcv_cbam_apply", "the map");
+    // A tile: R rows x CW columns, CW == W or R == 1 (a run of consecutive pixels) of about 8 K elements - the four chunks per thread
+    // the kernel holds in registers while it computes the tile's gate values - at most kCbamTilePix pixels, so that its 3-pixel
+    // halo fits kCbamHalo (cbam_kernels.hpp). The 56 x 56 x 256 map: 32 + 24 pixels of a row, a 7 x 38 halo.
+    const int PT = std::min(kCbamTilePix, std::max(4, kCbamPrefetch * 2048 / C));
+    CbamApplyParams q;
+    if (W <= PT) {
+        q.CW = W;
+        q.R = std::min(H, PT / W);
+    } else {
+        q.R = 1;
+        q.CW = PT;
+    }
+    if ((q.R + 6) * (q.CW + 6) > kCbamHalo || q.R * q.CW > kCbamTilePix) return fail(ctx, PCV_ERR_INVALID, "pcv_cbam_apply: tile plan");
+    q.tiles_h = (H + q.R - 1) / q.R;
+    q.tiles_w = (W + q.CW - 1) / q.CW;
+    q.tiles = (long)N * q.tiles_h * q.tiles_w;
+    if (q.tiles > 0x7fffffffl) return too_large(ctx, "pcv_cbam_apply", "the grid");
+    q.x = x; q.gate = gate; q.p = p; q.w7 = w7; q.res = residual; q.y = y;
+    q.scale = scale; q.shift = shift;
+    q.H = H; q.W = W; q.C = C;
+    q.post_act = post_act;
+    q.ovf = ctx->ovf;
+    long blocks = q.tiles;
+    if (ctx->max_blocks > 0 && blocks > ctx->max_blocks) blocks = ctx->max_blocks;      // multi-round tests only (as pcv_se_scale)
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == PCV_BF16) cbam_apply_kernel<PCV_BF16><<<(unsigned)blocks, 256, 0, st>>>(q);
+    else if (dtype == PCV_F16) cbam_apply_kernel<PCV_F16><<<(unsigned)blocks, 256, 0, st>>>(q);
+    else cbam_apply_kernel<PCV_F32><<<(unsigned)blocks, 256, 0, st>>>(q);
     HIP_TRY(ctx, hipGetLastError());
     return PCV_OK;
 }

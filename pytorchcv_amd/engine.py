@@ -5,7 +5,7 @@
 """
 
 __all__ = ['NHWC', 'DTYPES', 'default_dtype', 'set_compute_dtype', 'compute_dtype_of', 'Fp16Guard', 'fp16_overflow_count', 'from_nchw', 'to_nchw', 'ConvRunner',
-           'BnActRunner', 'maxpool2d', 'avgpool2d', 'avgpool2d_pad', 'global_avgpool', 'se_forward', 'splat_forward', 'channel_slice', 'cat_shuffle2', 'act_code',
+           'BnActRunner', 'maxpool2d', 'avgpool2d', 'avgpool2d_pad', 'global_avgpool', 'se_forward', 'splat_forward', 'cbam_forward', 'channel_slice', 'cat_shuffle2', 'act_code',
            'boundary', 'round8', 'channel_concat_into', 'interpolate', 'add', 'classify']
 
 import os
@@ -900,6 +900,34 @@ def splat_forward(x: NHWC, radix: int, groups: int, w1, b1, w2, b2, residual: NH
         raise RuntimeError("split-attention residual shape/dtype mismatch: {} vs {}".format(tuple(residual.t.shape), tuple(y.shape)))
     _lib.check(L.pcv_splat_combine(ctx, _ptr(x.t), _ptr(att), _ptr(residual.t) if residual is not None else None, _ptr(y), N, HW,
                                    C, radix, post_act, code, st), ctx)
+    return NHWC(y, N, x.H, x.W, C)
+
+
+def cbam_forward(x: NHWC, w1, b1, w2, b2, w7, scale, shift, residual: NHWC | None = None, post_act: int = 0) -> NHWC:
+    """CBAM block on the hot path (CbamBlock, reference cbamresnet.py:105-128): mean and max over the map -> shared fp32 MLP (w1 [M, C],
+    b1 [M], w2 [C, M], b2 [C]) on both, summed, sigmoid -> per-pixel max and mean over the channels of x * gate -> 7x7 convolution
+    2 -> 1 (w7 fp32 [2, 7, 7]; `scale` / `shift`: one device float each, its folded BatchNorm), sigmoid -> y = post_act((x * gate) *
+    spatial gate + residual). Four launches; the only tensor of x's size they write is y."""
+    if not x.dense or x.C % 8:
+        raise NotImplementedError("CBAM on {} channels: the MI355X path needs a dense handle with a multiple of 8".format(x.C))
+    L, ctx, st = _lib.lib(), _ctx(x.device), _stream(x.device)
+    code = _CODE_OF_TORCH[x.dtype]
+    N, HW, C, M = x.N, x.H * x.W, x.C, int(w1.shape[0])
+    if tuple(w1.shape) != (M, C) or tuple(w2.shape) != (C, M) or w7.numel() != 98 or scale.numel() != 1 or shift.numel() != 1:
+        raise RuntimeError("CBAM weights do not fit {} channels".format(C))
+    f32 = dict(dtype=torch.float32, device=x.device)
+    s = torch.empty((N, 2, C), **f32)
+    _lib.check(L.pcv_cbam_pool(ctx, _ptr(x.t), _ptr(s), N, HW, C, code, st), ctx)
+    mid = torch.empty((N, 2, M), **f32)
+    gate = torch.empty((N, C), **f32)
+    _lib.check(L.pcv_cbam_excite(ctx, _ptr(s), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(mid), _ptr(gate), N, C, M, st), ctx)
+    p = torch.empty((N, HW, 2), **f32)
+    _lib.check(L.pcv_cbam_spatial_pool(ctx, _ptr(x.t), _ptr(gate), _ptr(p), N, HW, C, code, st), ctx)
+    y = torch.empty_like(x.t)
+    if residual is not None and (tuple(residual.t.shape) != tuple(x.t.shape) or residual.dtype != x.dtype):
+        raise RuntimeError("CBAM residual shape/dtype mismatch: {} vs {}".format(tuple(residual.t.shape), tuple(x.t.shape)))
+    _lib.check(L.pcv_cbam_apply(ctx, _ptr(x.t), _ptr(gate), _ptr(p), _ptr(w7), _ptr(scale), _ptr(shift),
+                                _ptr(residual.t) if residual is not None else None, _ptr(y), N, x.H, x.W, C, post_act, code, st), ctx)
     return NHWC(y, N, x.H, x.W, C)
 
 

@@ -1,0 +1,213 @@
+"""
+    CBAM-ResNet for ImageNet-1K on the MI355X hot path (reference pytorchcv/models/cbamresnet.py:15-435). Module tree, attribute
+    names and factory signatures follow the reference so its state_dicts load strictly. A unit is the ResNet body (ResBlock /
+    ResBottleneck with the stride on conv2, run without its skip add) followed by the CBAM block as four launches (channel pools,
+    fp32 MLP, spatial pools of the channel-gated map, 7x7 spatial gate + both multiplications); the unit's skip add and ReLU ride in
+    the last one, so the block reads the body's output three times and writes the unit's output once.
+"""
+
+__all__ = ['CbamResNet', 'cbam_resnet18', 'cbam_resnet34', 'cbam_resnet50', 'cbam_resnet101', 'cbam_resnet152', 'MLP', 'ChannelGate',
+           'SpatialGate', 'CbamBlock', 'CbamResUnit', 'get_resnet']
+
+import torch
+import torch.nn as nn
+from .common.conv import conv1x1_block, conv7x7_block
+from .common.att import fold_bn_into_fc, _FoldedMlp
+from .resnet import ResInitBlock, ResBlock, ResBottleneck
+from ._tail import AvgPool2dNHWC, LinearHead, run_net, maybe_load_pretrained, init_conv_params, DEFAULT_ROOT
+from .. import engine, _lib
+
+
+class MLP(nn.Module):
+    """fc1 -> ReLU -> fc2 on [N, C] (reference cbamresnet.py:15-45); inside a ChannelGate it runs on both pooled rows at once
+    (pcv_cbam_excite). Called on its own with an fp32 device tensor [N, C(, 1, 1)] it is the two layers of pcv_se_excite."""
+    def __init__(self, channels, reduction_ratio=16):
+        super(MLP, self).__init__()
+        mid_channels = channels // reduction_ratio
+        self.fc1 = nn.Linear(in_features=channels, out_features=mid_channels)
+        self.activ = nn.ReLU(inplace=True)
+        self.fc2 = nn.Linear(in_features=mid_channels, out_features=channels)
+
+    def weights(self):
+        """fp32 (w1 [M, C], b1 [M], w2 [C, M], b2 [C]) as the excite launch reads them."""
+        return tuple(t.detach().float().contiguous() for t in (self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias))
+
+    def forward(self, x):
+        x = x.reshape(x.size(0), -1).float().contiguous()
+        w1, b1, w2, b2 = self.weights()
+        N, C, M = x.shape[0], w1.shape[1], w1.shape[0]
+        if x.shape[1] != C:
+            raise RuntimeError("MLP expects {} features, got {}".format(C, x.shape[1]))
+        mid = torch.empty((N, M), dtype=torch.float32, device=x.device)
+        y = torch.empty((N, C), dtype=torch.float32, device=x.device)
+        ctx, p = engine._ctx(x.device), engine._ptr
+        _lib.check(_lib.lib().pcv_se_excite(ctx, p(x), p(w1), p(b1), p(w2), p(b2), p(mid), p(y), N, C, M, engine.act_code(self.activ), 0,
+                                            engine._stream(x.device)), ctx)
+        return y
+
+
+class ChannelGate(nn.Module):
+    """x * sigmoid(mlp(avg_pool(x)) + mlp(max_pool(x))) (reference cbamresnet.py:48-80). The fp32 [N, C] factor takes two launches
+    (pcv_cbam_pool, pcv_cbam_excite); on its own the block multiplies by it in a third (pcv_se_scale), inside a CbamBlock the product
+    is never stored."""
+    def __init__(self, channels, reduction_ratio=16):
+        super(ChannelGate, self).__init__()
+        self.avg_pool = nn.AdaptiveAvgPool2d(output_size=(1, 1))      # markers only; pcv_cbam_pool computes both
+        self.max_pool = nn.AdaptiveMaxPool2d(output_size=(1, 1))
+        self.mlp = MLP(channels=channels, reduction_ratio=reduction_ratio)
+        self.sigmoid = nn.Sigmoid()
+
+    def _run(self, a):
+        if not a.dense or a.C % 8:
+            raise NotImplementedError("CBAM on {} channels: the MI355X path needs a dense handle with a multiple of 8".format(a.C))
+        w1, b1, w2, b2 = self.mlp.weights()
+        L, ctx, st, p = _lib.lib(), engine._ctx(a.device), engine._stream(a.device), engine._ptr
+        code = engine._CODE_OF_TORCH[a.dtype]
+        N, HW, C, M = a.N, a.H * a.W, a.C, w1.shape[0]
+        f32 = dict(dtype=torch.float32, device=a.device)
+        s, mid, gate = torch.empty((N, 2, C), **f32), torch.empty((N, 2, M), **f32), torch.empty((N, C), **f32)
+        _lib.check(L.pcv_cbam_pool(ctx, p(a.t), p(s), N, HW, C, code, st), ctx)
+        _lib.check(L.pcv_cbam_excite(ctx, p(s), p(w1), p(b1), p(w2), p(b2), p(mid), p(gate), N, C, M, st), ctx)
+        y = torch.empty_like(a.t)
+        _lib.check(L.pcv_se_scale(ctx, p(a.t), p(gate), None, p(y), N, HW, C, 0, code, st), ctx)
+        return engine.NHWC(y, N, a.H, a.W, C)
+
+    def forward(self, x):
+        return engine.boundary(self, x, self._run)
+
+
+class SpatialGate(nn.Module):
+    """x * sigmoid(bn(conv7x7(cat(max_c x, mean_c x)))) (reference cbamresnet.py:83-102). `conv` is a ConvBlock for its parameters
+    only (`conv.conv.weight` [1, 2, 7, 7], `conv.bn`): the 2 -> 1 convolution on a 25 KB map is a stencil inside pcv_cbam_apply."""
+    def __init__(self):
+        super(SpatialGate, self).__init__()
+        self.conv = conv7x7_block(in_channels=2, out_channels=1, activation=None)
+        self.sigmoid = nn.Sigmoid()
+        self._pcv_stencil = _FoldedMlp()
+
+    def stencil(self):
+        """fp32 (w7 [2, 7, 7], scale [1], shift [1]) on the parameters' device: the taps and the folded BatchNorm (+ bias) behind
+        them, re-derived whenever a source parameter changes."""
+        c, bn = self.conv.conv, (self.conv.bn if self.conv.normalize else None)
+        srcs = [c.weight, c.bias] + ([bn.weight, bn.bias, bn.running_mean, bn.running_var] if bn is not None else [])
+
+        def build():
+            # fold_bn_into_fc on a unit "weight" gives the affine map behind the convolution: scale = g / sqrt(var + eps), and the
+            # shift with the convolution's bias folded in
+            one = torch.ones((1, 1), dtype=torch.float32, device=c.weight.device)
+            scale, shift = fold_bn_into_fc(one, c.bias, bn)
+            return c.weight.detach().float().reshape(2, 7, 7).contiguous(), scale.reshape(1).contiguous(), shift.reshape(1).contiguous()
+        return self._pcv_stencil.get(srcs, build)
+
+    def _run(self, a):
+        if not a.dense or a.C % 8:
+            raise NotImplementedError("CBAM on {} channels: the MI355X path needs a dense handle with a multiple of 8".format(a.C))
+        w7, scale, shift = self.stencil()
+        L, ctx, st, p = _lib.lib(), engine._ctx(a.device), engine._stream(a.device), engine._ptr
+        code = engine._CODE_OF_TORCH[a.dtype]
+        N, HW, C = a.N, a.H * a.W, a.C
+        ones = torch.ones((N, C), dtype=torch.float32, device=a.device)
+        pm = torch.empty((N, HW, 2), dtype=torch.float32, device=a.device)
+        _lib.check(L.pcv_cbam_spatial_pool(ctx, p(a.t), p(ones), p(pm), N, HW, C, code, st), ctx)
+        y = torch.empty_like(a.t)
+        _lib.check(L.pcv_cbam_apply(ctx, p(a.t), p(ones), p(pm), p(w7), p(scale), p(shift), None, p(y), N, a.H, a.W, C, 0, code, st), ctx)
+        return engine.NHWC(y, N, a.H, a.W, C)
+
+    def forward(self, x):
+        return engine.boundary(self, x, self._run)
+
+
+class CbamBlock(nn.Module):
+    """ChannelGate then SpatialGate (reference cbamresnet.py:105-128) as engine.cbam_forward's four launches. `forward(x, residual=
+    None, post_act=None)` also takes the unit's skip tensor and the activation after the add: they ride in the last launch."""
+    def __init__(self, channels, reduction_ratio=16):
+        super(CbamBlock, self).__init__()
+        self.ch_gate = ChannelGate(channels=channels, reduction_ratio=reduction_ratio)
+        self.sp_gate = SpatialGate()
+
+    def _run(self, a, residual=None, post_act=None):
+        w1, b1, w2, b2 = self.ch_gate.mlp.weights()
+        w7, scale, shift = self.sp_gate.stencil()
+        return engine.cbam_forward(a, w1, b1, w2, b2, w7, scale, shift, residual, engine.act_code(post_act))
+
+    def forward(self, x, residual=None, post_act=None):
+        return engine.boundary(self, x, lambda a: self._run(a, residual, post_act))
+
+
+class CbamResUnit(nn.Module):
+    """relu(cbam(body(x)) + identity) (reference cbamresnet.py:131-183)."""
+    def __init__(self, in_channels, out_channels, stride, bottleneck):
+        super(CbamResUnit, self).__init__()
+        self.resize_identity = (in_channels != out_channels) or (stride != 1)
+        if bottleneck:
+            self.body = ResBottleneck(in_channels=in_channels, out_channels=out_channels, stride=stride, conv1_stride=False)
+        else:
+            self.body = ResBlock(in_channels=in_channels, out_channels=out_channels, stride=stride)
+        if self.resize_identity:
+            self.identity_conv = conv1x1_block(in_channels=in_channels, out_channels=out_channels, stride=stride, activation=None)
+        self.cbam = CbamBlock(channels=out_channels)
+        self.activ = nn.ReLU(inplace=True)
+
+    def _run(self, a):
+        identity = self.identity_conv(a) if self.resize_identity else a
+        return self.cbam(self.body(a), residual=identity, post_act=self.activ)      # the body without its own skip add
+
+    def forward(self, x):
+        return engine.boundary(self, x, self._run)
+
+
+class CbamResNet(nn.Module):
+    """`features` (init_block, stage1..4 of unit1..n, final_pool) + `output` Linear (reference cbamresnet.py:186-253)."""
+    def __init__(self, channels, init_block_channels, bottleneck, in_channels=3, in_size=(224, 224), num_classes=1000):
+        super(CbamResNet, self).__init__()
+        self.in_size = in_size
+        self.num_classes = num_classes
+        self.features = nn.Sequential()
+        self.features.add_module("init_block", ResInitBlock(in_channels=in_channels, out_channels=init_block_channels))
+        in_channels = init_block_channels
+        for i, channels_per_stage in enumerate(channels):
+            stage = nn.Sequential()
+            for j, out_channels in enumerate(channels_per_stage):
+                stride = 2 if (j == 0) and (i != 0) else 1
+                stage.add_module("unit{}".format(j + 1), CbamResUnit(in_channels=in_channels, out_channels=out_channels, stride=stride,
+                                                                     bottleneck=bottleneck))
+                in_channels = out_channels
+            self.features.add_module("stage{}".format(i + 1), stage)
+        self.features.add_module("final_pool", AvgPool2dNHWC(kernel_size=7, stride=1, fp32_out=True))
+        self.output = LinearHead(in_features=in_channels, out_features=num_classes)
+        init_conv_params(self)
+
+    def forward(self, x):
+        return run_net(self, x, self.output)
+
+
+def get_resnet(blocks, model_name=None, pretrained=False, root=DEFAULT_ROOT, **kwargs):
+    """CBAM-ResNet of a depth (the reference's factory and its name, cbamresnet.py:256-325)."""
+    layers = {18: [2, 2, 2, 2], 34: [3, 4, 6, 3], 50: [3, 4, 6, 3], 101: [3, 4, 23, 3], 152: [3, 8, 36, 3]}.get(blocks)
+    if layers is None:
+        raise ValueError("Unsupported CBAM-ResNet with number of blocks: {}".format(blocks))
+    bottleneck = blocks >= 50
+    widths = [256, 512, 1024, 2048] if bottleneck else [64, 128, 256, 512]
+    channels = [[w] * n for (w, n) in zip(widths, layers)]
+    net = CbamResNet(channels=channels, init_block_channels=64, bottleneck=bottleneck, **kwargs)
+    return maybe_load_pretrained(net, model_name, pretrained, root)
+
+
+def cbam_resnet18(**kwargs):
+    return get_resnet(blocks=18, model_name="cbam_resnet18", **kwargs)
+
+
+def cbam_resnet34(**kwargs):
+    return get_resnet(blocks=34, model_name="cbam_resnet34", **kwargs)
+
+
+def cbam_resnet50(**kwargs):
+    return get_resnet(blocks=50, model_name="cbam_resnet50", **kwargs)
+
+
+def cbam_resnet101(**kwargs):
+    return get_resnet(blocks=101, model_name="cbam_resnet101", **kwargs)
+
+
+def cbam_resnet152(**kwargs):
+    return get_resnet(blocks=152, model_name="cbam_resnet152", **kwargs)

@@ -2,6 +2,7 @@
 // (K-chunk tables, group blocking, tile choice) and kernel launches. No torch, no exceptions across the boundary.
 #include <hip/hip_runtime.h>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include <cstring>
 #include <algorithm>
@@ -140,12 +141,25 @@ struct DeviceGuard {
     }
 };
 
-static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
-// resident block slots of a persistent launch (CUs x blocks per CU), or the test cap of pcv_set_tuning("max_blocks")
-static inline long long block_slots(const pcv_ctx* ctx, int per_cu) {
-    const long long n = (long long)ctx->num_cu * per_cu;
-    return (ctx->max_blocks > 0 && ctx->max_blocks < n) ? ctx->max_blocks : n;
+// Every entry point that takes a context: a NULL context is refused without a message (there is nowhere to leave one), and the launches
+// go to the context's device for the rest of the function. Two statements, the second a declaration: only as the FIRST statement of a
+// function body.
+#define PCV_ENTER(ctx)                       \
+    if (!(ctx)) return PCV_ERR_INVALID;      \
+    DeviceGuard device_guard((ctx)->device)
+// ... and its last line after `<<<>>>` launches, which report through the runtime's sticky error
+static int launched(pcv_ctx* ctx) {
+    HIP_TRY(ctx, hipGetLastError());
+    return PCV_OK;
 }
+
+static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+// the test cap of pcv_set_tuning("max_blocks") on a grid of `blocks`
+static inline long long cap_blocks(const pcv_ctx* ctx, long long blocks) {
+    return (ctx->max_blocks > 0 && blocks > ctx->max_blocks) ? ctx->max_blocks : blocks;
+}
+// resident block slots of a persistent launch (CUs x blocks per CU), or that cap
+static inline long long block_slots(const pcv_ctx* ctx, int per_cu) { return cap_blocks(ctx, (long long)ctx->num_cu * per_cu); }
 static inline int esize(int dt) { return dt == PCV_F32 ? 4 : 2; }
 static inline bool dtype_ok(int dt) { return dt == PCV_F32 || dt == PCV_BF16 || dt == PCV_F16; }
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -155,6 +169,43 @@ static int too_large(pcv_ctx* ctx, const char* fn, const char* what) {
     return fail(ctx, PCV_ERR_TOO_LARGE, std::string(fn) + ": " + what + " exceeds the 2 GiB window of one launch; split the batch");
 }
 static const char* const kTensorTooLarge = "tensor exceeds the 2 GiB window";
+// Grid of a flat launch, one thread per item: ceil(total / per_block) blocks, refused where a 32-bit grid does not hold the count (or
+// the 64-bit product that gave `total` has wrapped to a negative value)
+static int flat_grid(pcv_ctx* ctx, const char* fn, long long total, unsigned* grid, int per_block = 256) {
+    const long long blocks = (total + per_block - 1) / per_block;
+    if (total < 0 || blocks > 0x7fffffffll) return too_large(ctx, fn, "the grid");
+    *grid = (unsigned)blocks;
+    return PCV_OK;
+}
+// Grid of a streaming kernel over `total` 16-byte chunks: one short-lived block per 256 chunks - fresh blocks read 6.2 TB/s where
+// grid-stride loops of resident blocks read 4.4 (tests/tools/micro/copy_bw2.cpp) - and the cap, which exists only so that the multi-round
+// tests can make each block walk several rounds (max_blocks)
+static int stream_grid(pcv_ctx* ctx, const char* fn, long long total, unsigned* grid) {
+    if (int rc = flat_grid(ctx, fn, total, grid)) return rc;
+    *grid = (unsigned)cap_blocks(ctx, *grid);
+    return PCV_OK;
+}
+// The storage type as a template argument: f(tag) is called with decltype(tag)::value == dt, so a launch site names its kernel family
+// once (`kernel<DT_OF(T)><<<...>>>(...)` inside a generic lambda). The entry points have checked dtype_ok(dt) before.
+template <int V> using dtype_tag = std::integral_constant<int, V>;
+#define DT_OF(tag) decltype(tag)::value
+template <class F> static void for_dtype(int dt, F&& f) {
+    if (dt == PCV_BF16) f(dtype_tag<PCV_BF16>{});
+    else if (dt == PCV_F16) f(dtype_tag<PCV_F16>{});
+    else f(dtype_tag<PCV_F32>{});
+}
+// the kernels that exist for the two 16-bit types only
+template <class F> static void for_dtype16(int dt, F&& f) {
+    if (dt == PCV_BF16) f(dtype_tag<PCV_BF16>{});
+    else f(dtype_tag<PCV_F16>{});
+}
+// input type x output type {the same, fp32}: f(in, out)
+template <class F> static void for_dtype_out(int dt, int ot, F&& f) {
+    for_dtype(dt, [&](auto T) {
+        if (ot == PCV_F32) f(T, dtype_tag<PCV_F32>{});
+        else f(T, T);
+    });
+}
 
 // One launchable kernel: entry point, block size, dynamic LDS bytes (the limit enable_kernels raises and the size launch() passes come
 // from this one field) and, where the family has tile shapes, output channels x pixels of a tile. Each family below has one table or
@@ -797,23 +848,26 @@ template <int DT, bool FAST> static void launch_dw2(const pcv_conv_desc& d, cons
     else if (d.stride_h == 1) dwconv5_kernel<DT, 1, FAST><<<grid, 256, 0, s>>>(p);     // 5x5: row streaming, 4 channels per thread
     else dwconv5_kernel<DT, 2, FAST><<<grid, 256, 0, s>>>(p);
 }
-template <int DT> static void launch_dw(const pcv_conv_desc& d, const DwParams& p, unsigned grid, hipStream_t s) {
-    if (d.act <= PCV_ACT_RELU6 && d.post_act <= PCV_ACT_RELU6) launch_dw2<DT, true>(d, p, grid, s);
-    else launch_dw2<DT, false>(d, p, grid, s);
+static void launch_dw(const pcv_conv_desc& d, const DwParams& p, unsigned grid, hipStream_t s) {
+    for_dtype(d.dtype, [&](auto T) {
+        if (d.act <= PCV_ACT_RELU6 && d.post_act <= PCV_ACT_RELU6) launch_dw2<DT_OF(T), true>(d, p, grid, s);
+        else launch_dw2<DT_OF(T), false>(d, p, grid, s);
+    });
 }
-// `radix` > 1: the split-attention squeeze over x with radix * C channels per pixel (pcv_splat_squeeze)
-template <int DT> static void launch_mean(const void* x, void* y, int N, int HW, int C, int ot, hipStream_t s, int radix = 1) {
+// `dt` -> `ot` (dt or fp32); `radix` > 1: the split-attention squeeze over x with radix * C channels per pixel (pcv_splat_squeeze)
+static void launch_mean(const void* x, void* y, int N, int HW, int C, int dt, int ot, hipStream_t s, int radix = 1) {
     dim3 grid((unsigned)N, (unsigned)((C / 8 + 511) / 512));
-    if (ot == PCV_F32) spatial_mean_kernel<DT, PCV_F32><<<grid, 512, 0, s>>>(x, y, HW, C, radix);
-    else spatial_mean_kernel<DT, DT><<<grid, 512, 0, s>>>(x, y, HW, C, radix);
+    for_dtype_out(dt, ot, [&](auto T, auto O) { spatial_mean_kernel<DT_OF(T), DT_OF(O)><<<grid, 512, 0, s>>>(x, y, HW, C, radix); });
 }
 // `pad` / `count_pad` / `ovf`: the padded pool of pcv_avgpool2d_pad (pcv_avgpool2d: no padding, no range counting)
-template <int DT> static void launch_avg(const void* x, void* y, int N, int H, int W, int C, int Ho, int Wo, int k, int s,
-                                         int ot, hipStream_t st, int pad = 0, int count_pad = 1, uint32_t* ovf = nullptr) {
-    const long total = (long)N * Ho * Wo * (C / 8);
-    const unsigned grid = (unsigned)((total + 255) / 256);
-    if (ot == PCV_F32) avgpool_kernel<DT, PCV_F32><<<grid, 256, 0, st>>>(x, y, N, H, W, C, Ho, Wo, k, s, pad, count_pad, ovf);
-    else avgpool_kernel<DT, DT><<<grid, 256, 0, st>>>(x, y, N, H, W, C, Ho, Wo, k, s, pad, count_pad, ovf);
+static int launch_avg(pcv_ctx* ctx, const char* fn, const void* x, void* y, int N, int H, int W, int C, int Ho, int Wo, int k, int s,
+                      int dt, int ot, hipStream_t st, int pad = 0, int count_pad = 1, uint32_t* ovf = nullptr) {
+    unsigned grid = 0;
+    if (int rc = flat_grid(ctx, fn, (long long)N * Ho * Wo * (C / 8), &grid)) return rc;
+    for_dtype_out(dt, ot, [&](auto T, auto O) {
+        avgpool_kernel<DT_OF(T), DT_OF(O)><<<grid, 256, 0, st>>>(x, y, N, H, W, C, Ho, Wo, k, s, pad, count_pad, ovf);
+    });
+    return launched(ctx);
 }
 
 
@@ -914,22 +968,18 @@ int pcv_destroy(pcv_ctx* ctx) {
 
 // ---- fp16 range guard ---------------------------------------------------------------------------------------
 int pcv_fp16_guard_begin(pcv_ctx* ctx, unsigned* slot, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!slot) return fail(ctx, PCV_ERR_INVALID, "pcv_fp16_guard_begin: slot is NULL");
     f16_guard_begin_kernel<<<1, 1, 0, (hipStream_t)stream>>>(ctx->ovf, slot);
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    return launched(ctx);
 }
 
 int pcv_fp16_guard_end(pcv_ctx* ctx, const unsigned* slot, float* y, long count, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!slot || !y || count <= 0) return fail(ctx, PCV_ERR_INVALID, "pcv_fp16_guard_end: bad argument");
     const unsigned grid = (unsigned)std::min<long>((count + 255) / 256, 1024);
     f16_guard_end_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(ctx->ovf, slot, y, count);
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    return launched(ctx);
 }
 
 // ---- RCCL helpers (resolved at run time: no link-time dependency) ----------------------------------------------
@@ -975,8 +1025,7 @@ int rccl_fail(pcv_ctx* ctx, const char* what, int rc) {
 int pcv_rccl_available(void) { return rccl_api().ok ? 1 : 0; }
 
 int pcv_rccl_broadcast(pcv_ctx* ctx, void* comm, void* const* bufs, const size_t* bytes, int count, int root, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!comm || !bufs || !bytes || count <= 0 || root < 0) return fail(ctx, PCV_ERR_INVALID, "pcv_rccl_broadcast: bad argument");
     for (int i = 0; i < count; ++i)
         if (!bufs[i] || bytes[i] == 0) return fail(ctx, PCV_ERR_INVALID, "pcv_rccl_broadcast: NULL or empty buffer");
@@ -992,8 +1041,7 @@ int pcv_rccl_broadcast(pcv_ctx* ctx, void* comm, void* const* bufs, const size_t
 }
 
 int pcv_rccl_allgather(pcv_ctx* ctx, void* comm, const void* send, void* recv, size_t bytes_per_rank, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!comm || !send || !recv || bytes_per_rank == 0) return fail(ctx, PCV_ERR_INVALID, "pcv_rccl_allgather: bad argument");
     const RcclApi& R = rccl_api();
     if (!R.ok) return fail(ctx, PCV_ERR_INVALID, "pcv_rccl_allgather: no RCCL in this process (librccl.so.1 not found)");
@@ -1003,8 +1051,7 @@ int pcv_rccl_allgather(pcv_ctx* ctx, void* comm, const void* send, void* recv, s
 }
 
 int pcv_fp16_overflow_count(pcv_ctx* ctx, unsigned* count, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!count) return fail(ctx, PCV_ERR_INVALID, "pcv_fp16_overflow_count: count is NULL");
     HIP_TRY(ctx, hipMemcpyAsync(count, ctx->ovf, sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)stream));
     HIP_TRY(ctx, hipStreamSynchronize((hipStream_t)stream));
@@ -1014,36 +1061,28 @@ int pcv_fp16_overflow_count(pcv_ctx* ctx, unsigned* count, void* stream) {
 // ---- layout ------------------------------------------------------------------------------------------------
 int pcv_nchw_to_nhwc(pcv_ctx* ctx, const float* x, void* y, int N, int C, int H, int W, int cpitch, int wpitch,
                      int dtype, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!x || !y || N <= 0 || C <= 0 || H <= 0 || W <= 0 || cpitch < C || wpitch < W || !dtype_ok(dtype))
         return fail(ctx, PCV_ERR_INVALID, "pcv_nchw_to_nhwc: bad argument");
     if (!(cpitch == 4 || cpitch % 8 == 0) && !(dtype == PCV_F32 && cpitch % 4 == 0))
         return fail(ctx, PCV_ERR_INVALID, "pcv_nchw_to_nhwc: cpitch must be 4 or a multiple of 8");
-    const long npix = (long)N * H * wpitch;
-    dim3 grid((unsigned)((npix + 255) / 256), (unsigned)((cpitch + 7) / 8));
+    dim3 grid(0, (unsigned)((cpitch + 7) / 8));
+    if (int rc = flat_grid(ctx, "pcv_nchw_to_nhwc", (long long)N * H * wpitch, &grid.x)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == PCV_BF16) nchw_to_nhwc_kernel<PCV_BF16><<<grid, 256, 0, s>>>(x, y, N, C, H, W, cpitch, wpitch, ctx->ovf);
-    else if (dtype == PCV_F16) nchw_to_nhwc_kernel<PCV_F16><<<grid, 256, 0, s>>>(x, y, N, C, H, W, cpitch, wpitch, ctx->ovf);
-    else nchw_to_nhwc_kernel<PCV_F32><<<grid, 256, 0, s>>>(x, y, N, C, H, W, cpitch, wpitch, ctx->ovf);
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    for_dtype(dtype, [&](auto T) { nchw_to_nhwc_kernel<DT_OF(T)><<<grid, 256, 0, s>>>(x, y, N, C, H, W, cpitch, wpitch, ctx->ovf); });
+    return launched(ctx);
 }
 
 int pcv_nhwc_to_nchw(pcv_ctx* ctx, const void* x, float* y, int N, int C, int H, int W, int cpitch, int dtype, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (cpitch <= 0) cpitch = C;
     if (!x || !y || N <= 0 || C <= 0 || H <= 0 || W <= 0 || cpitch < C || !dtype_ok(dtype))
         return fail(ctx, PCV_ERR_INVALID, "pcv_nhwc_to_nchw: bad argument");
-    const long total = (long)N * C * H * W;
-    const unsigned grid = (unsigned)((total + 255) / 256);
+    unsigned grid = 0;
+    if (int rc = flat_grid(ctx, "pcv_nhwc_to_nchw", (long long)N * C * H * W, &grid)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == PCV_BF16) nhwc_to_nchw_kernel<PCV_BF16><<<grid, 256, 0, s>>>(x, y, N, C, H, W, cpitch);
-    else if (dtype == PCV_F16) nhwc_to_nchw_kernel<PCV_F16><<<grid, 256, 0, s>>>(x, y, N, C, H, W, cpitch);
-    else nhwc_to_nchw_kernel<PCV_F32><<<grid, 256, 0, s>>>(x, y, N, C, H, W, cpitch);
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    for_dtype(dtype, [&](auto T) { nhwc_to_nchw_kernel<DT_OF(T)><<<grid, 256, 0, s>>>(x, y, N, C, H, W, cpitch); });
+    return launched(ctx);
 }
 
 // ---- weights -----------------------------------------------------------------------------------------------
@@ -1056,8 +1095,7 @@ int pcv_conv_packed_bytes(const pcv_conv_desc* d, size_t* bytes) {
 }
 
 int pcv_conv_pack(pcv_ctx* ctx, const pcv_conv_desc* d, const float* w, void* packed, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!d || !w || !packed) return fail(ctx, PCV_ERR_INVALID, "pcv_conv_pack: NULL argument");
     if (!aligned16(packed)) return fail(ctx, PCV_ERR_INVALID, "pcv_conv_pack: packed buffer must be 16-byte aligned");
     ConvPlan P;
@@ -1066,11 +1104,14 @@ int pcv_conv_pack(pcv_ctx* ctx, const pcv_conv_desc* d, const float* w, void* pa
     hipStream_t s = (hipStream_t)stream;
     if (P.stem) {
         const int total = d->kh * 64 * 32;
-        if (d->dtype == PCV_BF16) pack_stem_kernel<PCV_BF16><<<(total + 255) / 256, 256, 0, s>>>(w, packed, d->Cout, d->Cin, d->kh, d->kw, d->pad_l & 1);
-        else pack_stem_kernel<PCV_F16><<<(total + 255) / 256, 256, 0, s>>>(w, packed, d->Cout, d->Cin, d->kh, d->kw, d->pad_l & 1);
-        HIP_TRY(ctx, hipGetLastError());
-        return PCV_OK;
+        for_dtype16(d->dtype, [&](auto T) {
+            pack_stem_kernel<DT_OF(T)><<<(total + 255) / 256, 256, 0, s>>>(w, packed, d->Cout, d->Cin, d->kh, d->kw, d->pad_l & 1);
+        });
+        return launched(ctx);
     }
+    unsigned grid = 0, ggrid = 0;
+    if (int rc = flat_grid(ctx, "pcv_conv_pack", (long long)P.ngb * P.wrows * P.Kpad, &grid)) return rc;
+    if (int rc = flat_grid(ctx, "pcv_conv_pack", P.gconv ? (long long)(d->Cin / 16) * P.gconv_kt * 16 * 32 : 0, &ggrid)) return rc;
     // load-time only: synchronous uploads of the two small host-built tables
     uint32_t* ksrc_dev = nullptr;
     HIP_TRY(ctx, hipStreamSynchronize(s));
@@ -1093,21 +1134,13 @@ int pcv_conv_pack(pcv_ctx* ctx, const pcv_conv_desc* d, const float* w, void* pa
     pp.Cg_in = P.Cg_in;
     pp.Cg_out = P.Cg_out;
     pp.khkw = d->kh * d->kw;
-    const long total = (long)P.ngb * P.wrows * P.Kpad;
-    const unsigned grid = (unsigned)((total + 255) / 256);
-    if (d->dtype == PCV_BF16) pack_conv_kernel<PCV_BF16><<<grid, 256, 0, s>>>(pp);
-    else if (d->dtype == PCV_F16) pack_conv_kernel<PCV_F16><<<grid, 256, 0, s>>>(pp);
-    else pack_conv_kernel<PCV_F32><<<grid, 256, 0, s>>>(pp);
+    for_dtype(d->dtype, [&](auto T) { pack_conv_kernel<DT_OF(T)><<<grid, 256, 0, s>>>(pp); });
     if (P.gconv) {
-        const long gtotal = (long)(d->Cin / 16) * P.gconv_kt * 16 * 32;
-        const unsigned ggrid = (unsigned)((gtotal + 255) / 256);
         void* gout = static_cast<char*>(packed) + P.gconv_off;
-        const bool bf = d->dtype == PCV_BF16;
-        if (P.gconv_kt == 9) {
-            if (bf) pack_gconv32_kernel<PCV_BF16><<<ggrid, 256, 0, s>>>(w, gout, d->Cin);
-            else pack_gconv32_kernel<PCV_F16><<<ggrid, 256, 0, s>>>(w, gout, d->Cin);
-        } else if (bf) pack_gconv_kernel<PCV_BF16><<<ggrid, 256, 0, s>>>(w, gout, d->Cin, P.Cg_in);
-        else pack_gconv_kernel<PCV_F16><<<ggrid, 256, 0, s>>>(w, gout, d->Cin, P.Cg_in);
+        for_dtype16(d->dtype, [&](auto T) {
+            if (P.gconv_kt == 9) pack_gconv32_kernel<DT_OF(T)><<<ggrid, 256, 0, s>>>(w, gout, d->Cin);
+            else pack_gconv_kernel<DT_OF(T)><<<ggrid, 256, 0, s>>>(w, gout, d->Cin, P.Cg_in);
+        });
     }
     if (P.d3i || P.d1i) {
         const int total = (int)((P.total_bytes - P.d3i_off) / 16);
@@ -1148,37 +1181,31 @@ int pcv_dwconv_packed_bytes(const pcv_conv_desc* d, size_t* bytes) {
 }
 
 int pcv_dwconv_pack(pcv_ctx* ctx, const pcv_conv_desc* d, const float* w, void* packed, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!d || !w || !packed) return fail(ctx, PCV_ERR_INVALID, "pcv_dwconv_pack: NULL argument");
     const char* why = check_dw(*d);
     if (why) return fail(ctx, PCV_ERR_INVALID, std::string("pcv_dwconv_pack: ") + why);
-    const int total = d->Cin * d->kh * d->kw;
-    const unsigned grid = (unsigned)((total + 255) / 256);
+    unsigned grid = 0;
+    if (int rc = flat_grid(ctx, "pcv_dwconv_pack", (long long)d->Cin * d->kh * d->kw, &grid)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (d->dtype == PCV_BF16) pack_dw_kernel<PCV_BF16><<<grid, 256, 0, s>>>(w, packed, d->Cin, d->kh * d->kw);
-    else if (d->dtype == PCV_F16) pack_dw_kernel<PCV_F16><<<grid, 256, 0, s>>>(w, packed, d->Cin, d->kh * d->kw);
-    else pack_dw_kernel<PCV_F32><<<grid, 256, 0, s>>>(w, packed, d->Cin, d->kh * d->kw);
+    for_dtype(d->dtype, [&](auto T) { pack_dw_kernel<DT_OF(T)><<<grid, 256, 0, s>>>(w, packed, d->Cin, d->kh * d->kw); });
     if (dw_sparse_bytes(*d) != 0) {
         const int nChunks = (d->Cin + 31) / 32;
         pack_dw_sparse_kernel<<<(unsigned)((nChunks * 6 * 64 + 255) / 256), 256, 0, s>>>(
             static_cast<const uint16_t*>(packed), reinterpret_cast<u32x4*>(static_cast<char*>(packed) + dw_taps_bytes(*d)), d->Cin, nChunks);
     }
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    return launched(ctx);
 }
 
 int pcv_bn_fold(pcv_ctx* ctx, int C, const float* gamma, const float* beta, const float* mean, const float* var,
                 float eps, const float* conv_bias, float* scale, float* shift, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (C <= 0 || !scale || !shift) return fail(ctx, PCV_ERR_INVALID, "pcv_bn_fold: bad argument");
     const bool any = gamma || beta || mean || var;
     const bool all = gamma && beta && mean && var;
     if (any && !all) return fail(ctx, PCV_ERR_INVALID, "pcv_bn_fold: gamma/beta/mean/var must be all set or all NULL");
     bn_fold_kernel<<<(C + 255) / 256, 256, 0, (hipStream_t)stream>>>(C, gamma, beta, mean, var, eps, conv_bias, scale, shift);
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    return launched(ctx);
 }
 
 // ---- hot path ----------------------------------------------------------------------------------------------
@@ -1534,8 +1561,7 @@ static int launch_head(pcv_ctx* ctx, const pcv_conv_desc* d, const ConvPlan& P, 
     const bool wide = (long long)gx * ((d->N + 31) / 32) >= 2ll * ctx->num_cu;      // enough 32-image blocks for two per CU
     if (wide) hipLaunchKernelGGL(head_gemm_f32_kernel<32>, dim3(gx, (unsigned)((d->N + 31) / 32)), dim3(256), 0, A.stream, q);
     else hipLaunchKernelGGL(head_gemm_f32_kernel<16>, dim3(gx, (unsigned)((d->N + 15) / 16)), dim3(256), 0, A.stream, q);
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    return launched(ctx);
 }
 
 static int launch_igemm(pcv_ctx* ctx, const pcv_conv_desc* d, const ConvPlan& P, const ConvGeom& G, const ConvArgs& A, const ConvRoute& R) {
@@ -1612,8 +1638,7 @@ static int launch_igemm(pcv_ctx* ctx, const pcv_conv_desc* d, const ConvPlan& P,
 static int conv2d_impl(pcv_ctx* ctx, const pcv_conv_desc* d, const void* x, const void* packed, const float* scale,
                        const float* shift, const void* residual, void* y, void* stream, bool pool, const float* gate = nullptr,
                        bool x_nchw = false) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!d || !x || !packed || !y) return fail(ctx, PCV_ERR_INVALID, "pcv_conv2d_fused: NULL argument");
     if (d->has_residual && !residual) return fail(ctx, PCV_ERR_INVALID, "pcv_conv2d_fused: has_residual but residual is NULL");
     if (d->N <= 0 || d->H <= 0 || d->W <= 0) return fail(ctx, PCV_ERR_INVALID, "pcv_conv2d_fused: empty input");
@@ -1669,12 +1694,10 @@ int pcv_conv2d_gated_fused(pcv_ctx* ctx, const pcv_conv_desc* d, const void* x, 
 
 int pcv_fc_f32(pcv_ctx* ctx, const float* in, const float* w, const float* b, float* out, int N, int K, int J, int act,
                void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!in || !w || !b || !out || N <= 0 || K <= 0 || J <= 0) return fail(ctx, PCV_ERR_INVALID, "pcv_fc_f32: bad argument");
     launch_se_fc(in, w, b, out, N, K, J, act, (hipStream_t)stream);
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    return launched(ctx);
 }
 
 int pcv_conv2d_maxpool_supported(const pcv_conv_desc* d, int k, int s, int p, int ceil_mode) {
@@ -1711,8 +1734,7 @@ int pcv_conv2d_nchw_stem_fused(pcv_ctx* ctx, const pcv_conv_desc* d, const float
 
 int pcv_dwconv2d_fused(pcv_ctx* ctx, const pcv_conv_desc* d, const void* x, const void* packed, const float* scale,
                        const float* shift, const void* residual, void* y, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!d || !x || !packed || !y || !scale || !shift) return fail(ctx, PCV_ERR_INVALID, "pcv_dwconv2d_fused: NULL argument");
     const char* why = check_dw(*d);
     if (why) return fail(ctx, PCV_ERR_INVALID, std::string("pcv_dwconv2d_fused: ") + why);
@@ -1752,13 +1774,10 @@ int pcv_dwconv2d_fused(pcv_ctx* ctx, const pcv_conv_desc* d, const void* x, cons
     p.post_act = d->post_act;
     p.total = cols * p.nseg;
     p.flags = ctx->dw_flags;
-    const unsigned grid = (unsigned)((p.total + 255) / 256);
-    hipStream_t s = (hipStream_t)stream;
-    if (d->dtype == PCV_BF16) launch_dw<PCV_BF16>(*d, p, grid, s);
-    else if (d->dtype == PCV_F16) launch_dw<PCV_F16>(*d, p, grid, s);
-    else launch_dw<PCV_F32>(*d, p, grid, s);
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    unsigned grid = 0;
+    if (int rc = flat_grid(ctx, "pcv_dwconv2d_fused", p.total, &grid)) return rc;
+    launch_dw(*d, p, grid, (hipStream_t)stream);
+    return launched(ctx);
 }
 
 static int pool_out(int in, int k, int s, int p, int ceil_mode) {
@@ -1771,63 +1790,44 @@ static int pool_out(int in, int k, int s, int p, int ceil_mode) {
 
 int pcv_maxpool2d(pcv_ctx* ctx, const void* x, void* y, int N, int H, int W, int C, int k, int s, int p, int ceil_mode,
                   int dtype, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!x || !y || N <= 0 || H <= 0 || W <= 0 || C <= 0 || k <= 0 || s <= 0 || p < 0 || !dtype_ok(dtype) || C % 8 != 0 ||
         2 * p > k)
         return fail(ctx, PCV_ERR_INVALID, "pcv_maxpool2d: bad argument (C must be a multiple of 8, pad <= k/2)");
     const int Ho = pool_out(H, k, s, p, ceil_mode), Wo = pool_out(W, k, s, p, ceil_mode);
     if (Ho <= 0 || Wo <= 0) return fail(ctx, PCV_ERR_INVALID, "pcv_maxpool2d: empty output");
-    const long total = (long)N * Ho * Wo * (C / 8);
-    const unsigned grid = (unsigned)((total + 255) / 256);
+    unsigned grid = 0;
+    if (int rc = flat_grid(ctx, "pcv_maxpool2d", (long long)N * Ho * Wo * (C / 8), &grid)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == PCV_BF16) maxpool_kernel<PCV_BF16><<<grid, 256, 0, st>>>(x, y, N, H, W, C, Ho, Wo, k, s, p);
-    else if (dtype == PCV_F16) maxpool_kernel<PCV_F16><<<grid, 256, 0, st>>>(x, y, N, H, W, C, Ho, Wo, k, s, p);
-    else maxpool_kernel<PCV_F32><<<grid, 256, 0, st>>>(x, y, N, H, W, C, Ho, Wo, k, s, p);
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    for_dtype(dtype, [&](auto T) { maxpool_kernel<DT_OF(T)><<<grid, 256, 0, st>>>(x, y, N, H, W, C, Ho, Wo, k, s, p); });
+    return launched(ctx);
 }
 
 int pcv_avgpool2d(pcv_ctx* ctx, const void* x, void* y, int N, int H, int W, int C, int k, int s, int dtype,
                   int out_dtype, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!x || !y || N <= 0 || H <= 0 || W <= 0 || C <= 0 || k <= 0 || s <= 0 || !dtype_ok(dtype) || C % 8 != 0 ||
         (out_dtype != dtype && out_dtype != PCV_F32) || k > H || k > W)
         return fail(ctx, PCV_ERR_INVALID, "pcv_avgpool2d: bad argument (C must be a multiple of 8, k <= H,W)");
     hipStream_t st = (hipStream_t)stream;
     const int Ho = (H - k) / s + 1, Wo = (W - k) / s + 1;
-    if (k == H && k == W) {
-        if (dtype == PCV_BF16) launch_mean<PCV_BF16>(x, y, N, H * W, C, out_dtype, st);
-        else if (dtype == PCV_F16) launch_mean<PCV_F16>(x, y, N, H * W, C, out_dtype, st);
-        else launch_mean<PCV_F32>(x, y, N, H * W, C, out_dtype, st);
-    } else {
-        if (dtype == PCV_BF16) launch_avg<PCV_BF16>(x, y, N, H, W, C, Ho, Wo, k, s, out_dtype, st);
-        else if (dtype == PCV_F16) launch_avg<PCV_F16>(x, y, N, H, W, C, Ho, Wo, k, s, out_dtype, st);
-        else launch_avg<PCV_F32>(x, y, N, H, W, C, Ho, Wo, k, s, out_dtype, st);
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    if (k != H || k != W) return launch_avg(ctx, "pcv_avgpool2d", x, y, N, H, W, C, Ho, Wo, k, s, dtype, out_dtype, st);
+    launch_mean(x, y, N, H * W, C, dtype, out_dtype, st);
+    return launched(ctx);
 }
 
 int pcv_global_avgpool(pcv_ctx* ctx, const void* x, void* y, int N, int HW, int C, int dtype, int out_dtype, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!x || !y || N <= 0 || HW <= 0 || C <= 0 || C % 8 != 0 || !dtype_ok(dtype) ||
         (out_dtype != dtype && out_dtype != PCV_F32))
         return fail(ctx, PCV_ERR_INVALID, "pcv_global_avgpool: bad argument (C must be a multiple of 8)");
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == PCV_BF16) launch_mean<PCV_BF16>(x, y, N, HW, C, out_dtype, st);
-    else if (dtype == PCV_F16) launch_mean<PCV_F16>(x, y, N, HW, C, out_dtype, st);
-    else launch_mean<PCV_F32>(x, y, N, HW, C, out_dtype, st);
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    launch_mean(x, y, N, HW, C, dtype, out_dtype, (hipStream_t)stream);
+    return launched(ctx);
 }
 
 int pcv_gemm_bias(pcv_ctx* ctx, const void* x, const void* packed, const float* bias, void* y, int N, int Cin,
                   int Cout, int dtype, int out_dtype, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     pcv_conv_desc d;
     std::memset(&d, 0, sizeof(d));
     d.N = N; d.H = 1; d.W = 1; d.Cin = Cin; d.Cout = Cout; d.kh = 1; d.kw = 1;
@@ -1838,16 +1838,11 @@ int pcv_gemm_bias(pcv_ctx* ctx, const void* x, const void* packed, const float* 
 }
 
 int pcv_se_squeeze(pcv_ctx* ctx, const void* x, float* mean, int N, int HW, int C, int dtype, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!x || !mean || N <= 0 || HW <= 0 || C <= 0 || C % 8 != 0 || !dtype_ok(dtype))
         return fail(ctx, PCV_ERR_INVALID, "pcv_se_squeeze: bad argument (C must be a multiple of 8)");
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == PCV_BF16) launch_mean<PCV_BF16>(x, mean, N, HW, C, PCV_F32, st);
-    else if (dtype == PCV_F16) launch_mean<PCV_F16>(x, mean, N, HW, C, PCV_F32, st);
-    else launch_mean<PCV_F32>(x, mean, N, HW, C, PCV_F32, st);
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    launch_mean(x, mean, N, HW, C, dtype, PCV_F32, (hipStream_t)stream);
+    return launched(ctx);
 }
 
 static void launch_se_fc(const float* in, const float* w, const float* b, float* out, int N, int K, int J, int act,
@@ -1862,84 +1857,66 @@ static void launch_se_fc(const float* in, const float* w, const float* b, float*
 
 int pcv_se_excite(pcv_ctx* ctx, const float* mean, const float* w1, const float* b1, const float* w2, const float* b2,
                   float* mid, float* gate, int N, int C, int M, int mid_act, int out_act, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!mean || !w1 || !b1 || !w2 || !b2 || !mid || !gate || N <= 0 || C <= 0 || M <= 0)
         return fail(ctx, PCV_ERR_INVALID, "pcv_se_excite: bad argument");
     hipStream_t st = (hipStream_t)stream;
     launch_se_fc(mean, w1, b1, mid, N, C, M, mid_act, st);
     launch_se_fc(mid, w2, b2, gate, N, M, C, out_act, st);
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    return launched(ctx);
 }
 
 int pcv_se_scale(pcv_ctx* ctx, const void* x, const float* gate, const void* residual, void* y, int N, int HW, int C,
                  int post_act, int dtype, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!x || !gate || !y || N <= 0 || HW <= 0 || C <= 0 || C % 8 != 0 || !dtype_ok(dtype))
         return fail(ctx, PCV_ERR_INVALID, "pcv_se_scale: bad argument (C must be a multiple of 8)");
     const long total8 = (long)N * HW * (C / 8);
-    long blocks = (total8 + 255) / 256;
-    // one short-lived block per 256 chunks: a streaming kernel of fresh blocks reads 6.2 TB/s where grid-stride loops of resident
-    // blocks read 4.4 (tests/tools/micro/copy_bw2.cpp); the cap only exists for the multi-round tests (max_blocks)
-    if (ctx->max_blocks > 0 && blocks > ctx->max_blocks) blocks = ctx->max_blocks;
+    unsigned blocks = 0;
+    if (int rc = stream_grid(ctx, "pcv_se_scale", total8, &blocks)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == PCV_BF16) se_scale_kernel<PCV_BF16><<<(unsigned)blocks, 256, 0, st>>>(x, gate, residual, y, total8, HW, C, post_act, ctx->ovf);
-    else if (dtype == PCV_F16) se_scale_kernel<PCV_F16><<<(unsigned)blocks, 256, 0, st>>>(x, gate, residual, y, total8, HW, C, post_act, ctx->ovf);
-    else se_scale_kernel<PCV_F32><<<(unsigned)blocks, 256, 0, st>>>(x, gate, residual, y, total8, HW, C, post_act, ctx->ovf);
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    for_dtype(dtype, [&](auto T) { se_scale_kernel<DT_OF(T)><<<blocks, 256, 0, st>>>(x, gate, residual, y, total8, HW, C, post_act, ctx->ovf); });
+    return launched(ctx);
 }
 
 // ---- split attention (att.py:172-189, sknet.py:59-83) and the padded average pool (resnesta.py:45-48,138-142) ---------------
 int pcv_splat_squeeze(pcv_ctx* ctx, const void* x, float* s, int N, int HW, int C, int radix, int dtype, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!x || !s || N <= 0 || HW <= 0 || C <= 0 || C % 8 != 0 || radix < 1 || radix > 4 || !dtype_ok(dtype))
         return fail(ctx, PCV_ERR_INVALID, "pcv_splat_squeeze: bad argument (C must be a multiple of 8, radix in [1, 4])");
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == PCV_BF16) launch_mean<PCV_BF16>(x, s, N, HW, C, PCV_F32, st, radix);
-    else if (dtype == PCV_F16) launch_mean<PCV_F16>(x, s, N, HW, C, PCV_F32, st, radix);
-    else launch_mean<PCV_F32>(x, s, N, HW, C, PCV_F32, st, radix);
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    launch_mean(x, s, N, HW, C, dtype, PCV_F32, (hipStream_t)stream, radix);
+    return launched(ctx);
 }
 
 int pcv_splat_excite(pcv_ctx* ctx, const float* s, const float* w1, const float* b1, const float* w2, const float* b2, float* mid,
                      float* logits, float* att, int N, int C, int M, int radix, int groups, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!s || !w1 || !b1 || !w2 || !b2 || !mid || !logits || !att || N <= 0 || C <= 0 || C % 8 != 0 || M <= 0 || radix < 1 ||
         radix > 4 || groups < 1 || C % groups != 0)
         return fail(ctx, PCV_ERR_INVALID, "pcv_splat_excite: bad argument (C must be a multiple of 8 and of groups, radix in [1, 4])");
+    unsigned grid = 0;
+    if (int rc = flat_grid(ctx, "pcv_splat_excite", (long long)N * C, &grid)) return rc;
     hipStream_t st = (hipStream_t)stream;
     launch_se_fc(s, w1, b1, mid, N, C, M, PCV_ACT_RELU, st);
     launch_se_fc(mid, w2, b2, logits, N, M, radix * C, PCV_ACT_NONE, st);
-    const long total = (long)N * C;
-    splat_softmax_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(logits, att, N, C, radix, C / groups);
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    splat_softmax_kernel<<<grid, 256, 0, st>>>(logits, att, N, C, radix, C / groups);
+    return launched(ctx);
 }
 
 int pcv_splat_combine(pcv_ctx* ctx, const void* x, const float* att, const void* residual, void* y, int N, int HW, int C, int radix,
                       int post_act, int dtype, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!x || !att || !y || N <= 0 || HW <= 0 || C <= 0 || C % 8 != 0 || radix < 1 || radix > 4 || !dtype_ok(dtype) ||
         post_act < PCV_ACT_NONE || post_act > PCV_ACT_HSWISH)
         return fail(ctx, PCV_ERR_INVALID, "pcv_splat_combine: bad argument (C must be a multiple of 8, radix in [1, 4])");
     const long total8 = (long)N * HW * (C / 8);
-    long blocks = (total8 + 255) / 256;
-    if (ctx->max_blocks > 0 && blocks > ctx->max_blocks) blocks = ctx->max_blocks;      // multi-round tests only (as pcv_se_scale)
+    unsigned blocks = 0;
+    if (int rc = stream_grid(ctx, "pcv_splat_combine", total8, &blocks)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == PCV_BF16)
-        splat_combine_kernel<PCV_BF16><<<(unsigned)blocks, 256, 0, st>>>(x, att, residual, y, total8, HW, C, radix, post_act, ctx->ovf);
-    else if (dtype == PCV_F16)
-        splat_combine_kernel<PCV_F16><<<(unsigned)blocks, 256, 0, st>>>(x, att, residual, y, total8, HW, C, radix, post_act, ctx->ovf);
-    else splat_combine_kernel<PCV_F32><<<(unsigned)blocks, 256, 0, st>>>(x, att, residual, y, total8, HW, C, radix, post_act, ctx->ovf);
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    for_dtype(dtype, [&](auto T) {
+        splat_combine_kernel<DT_OF(T)><<<blocks, 256, 0, st>>>(x, att, residual, y, total8, HW, C, radix, post_act, ctx->ovf);
+    });
+    return launched(ctx);
 }
 
 // ---- CBAM (cbamresnet.py:48-128): four launches, no tensor of x's size written but y (cbam_kernels.hpp). Like the other aux kernels
@@ -1947,23 +1924,18 @@ int pcv_splat_combine(pcv_ctx* ctx, const void* x, const float* att, const void*
 static inline bool cbam_shape_ok(int N, long HW, int C) { return N > 0 && HW > 0 && C >= 8 && C % 8 == 0; }
 
 int pcv_cbam_pool(pcv_ctx* ctx, const void* x, float* s, int N, int HW, int C, int dtype, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!x || !s || !cbam_shape_ok(N, HW, C) || !dtype_ok(dtype))
         return fail(ctx, PCV_ERR_INVALID, "pcv_cbam_pool: bad argument (C must be a multiple of 8)");
     hipStream_t st = (hipStream_t)stream;
     dim3 grid((unsigned)N, (unsigned)((C / 8 + 511) / 512));
-    if (dtype == PCV_BF16) cbam_pool_kernel<PCV_BF16><<<grid, 512, 0, st>>>(x, s, HW, C);
-    else if (dtype == PCV_F16) cbam_pool_kernel<PCV_F16><<<grid, 512, 0, st>>>(x, s, HW, C);
-    else cbam_pool_kernel<PCV_F32><<<grid, 512, 0, st>>>(x, s, HW, C);
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    for_dtype(dtype, [&](auto T) { cbam_pool_kernel<DT_OF(T)><<<grid, 512, 0, st>>>(x, s, HW, C); });
+    return launched(ctx);
 }
 
 int pcv_cbam_excite(pcv_ctx* ctx, const float* s, const float* w1, const float* b1, const float* w2, const float* b2, float* mid,
                     float* gate, int N, int C, int M, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!s || !w1 || !b1 || !w2 || !b2 || !mid || !gate || !cbam_shape_ok(N, 1, C) || M < 1 || N > (1 << 30))
         return fail(ctx, PCV_ERR_INVALID, "pcv_cbam_excite: bad argument (C must be a multiple of 8, M >= 1)");
     if ((N + 7) / 8 > 65535) return too_large(ctx, "pcv_cbam_excite", "the batch");
@@ -1971,13 +1943,11 @@ int pcv_cbam_excite(pcv_ctx* ctx, const float* s, const float* w1, const float* 
     launch_se_fc(s, w1, b1, mid, 2 * N, C, M, PCV_ACT_RELU, st);          // the mean row and the max row of every image: s is [2N][C]
     dim3 grid((unsigned)((C + 255) / 256), (unsigned)((N + 7) / 8));
     cbam_gate_kernel<<<grid, 256, 0, st>>>(mid, w2, b2, gate, N, C, M);
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    return launched(ctx);
 }
 
 int pcv_cbam_spatial_pool(pcv_ctx* ctx, const void* x, const float* gate, float* p, int N, int HW, int C, int dtype, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!x || !gate || !p || !cbam_shape_ok(N, HW, C) || !dtype_ok(dtype))
         return fail(ctx, PCV_ERR_INVALID, "pcv_cbam_spatial_pool: bad argument (C must be a multiple of 8)");
     int LP = 1;
@@ -1987,20 +1957,16 @@ int pcv_cbam_spatial_pool(pcv_ctx* ctx, const void* x, const float* gate, float*
     int ppb = std::max(slots, 16384 / C);
     ppb = (ppb + slots - 1) / slots * slots;
     const int bpi = (HW + ppb - 1) / ppb;
-    const long long blocks = (long long)N * bpi;
-    if (blocks > 0x7fffffffll) return too_large(ctx, "pcv_cbam_spatial_pool", "the grid");
+    unsigned blocks = 0;
+    if (int rc = flat_grid(ctx, "pcv_cbam_spatial_pool", (long long)N * bpi, &blocks, 1)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == PCV_BF16) cbam_spatial_pool_kernel<PCV_BF16><<<(unsigned)blocks, 256, 0, st>>>(x, gate, p, HW, C, LP, ppb, bpi);
-    else if (dtype == PCV_F16) cbam_spatial_pool_kernel<PCV_F16><<<(unsigned)blocks, 256, 0, st>>>(x, gate, p, HW, C, LP, ppb, bpi);
-    else cbam_spatial_pool_kernel<PCV_F32><<<(unsigned)blocks, 256, 0, st>>>(x, gate, p, HW, C, LP, ppb, bpi);
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    for_dtype(dtype, [&](auto T) { cbam_spatial_pool_kernel<DT_OF(T)><<<blocks, 256, 0, st>>>(x, gate, p, HW, C, LP, ppb, bpi); });
+    return launched(ctx);
 }
 
 int pcv_cbam_apply(pcv_ctx* ctx, const void* x, const float* gate, const float* p, const float* w7, const float* scale, const float* shift,
                    const void* residual, void* y, int N, int H, int W, int C, int post_act, int dtype, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!x || !gate || !p || !w7 || !scale || !shift || !y || N <= 0 || H <= 0 || W <= 0 || C < 8 || C % 8 != 0 || !dtype_ok(dtype) ||
         post_act < PCV_ACT_NONE || post_act > PCV_ACT_HSWISH)
         return fail(ctx, PCV_ERR_INVALID, "pcv_cbam_apply: bad argument (C must be a multiple of 8)");
@@ -2027,20 +1993,15 @@ int pcv_cbam_apply(pcv_ctx* ctx, const void* x, const float* gate, const float* 
     q.H = H; q.W = W; q.C = C;
     q.post_act = post_act;
     q.ovf = ctx->ovf;
-    long blocks = q.tiles;
-    if (ctx->max_blocks > 0 && blocks > ctx->max_blocks) blocks = ctx->max_blocks;      // multi-round tests only (as pcv_se_scale)
+    const unsigned blocks = (unsigned)cap_blocks(ctx, q.tiles);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == PCV_BF16) cbam_apply_kernel<PCV_BF16><<<(unsigned)blocks, 256, 0, st>>>(q);
-    else if (dtype == PCV_F16) cbam_apply_kernel<PCV_F16><<<(unsigned)blocks, 256, 0, st>>>(q);
-    else cbam_apply_kernel<PCV_F32><<<(unsigned)blocks, 256, 0, st>>>(q);
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    for_dtype(dtype, [&](auto T) { cbam_apply_kernel<DT_OF(T)><<<blocks, 256, 0, st>>>(q); });
+    return launched(ctx);
 }
 
 int pcv_avgpool2d_pad(pcv_ctx* ctx, const void* x, void* y, int N, int H, int W, int C, int k, int s, int p, int ceil_mode,
                       int count_include_pad, int dtype, int out_dtype, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!x || !y || N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 != 0 || k <= 0 || s <= 0 || p < 0 || 2 * p > k ||
         !dtype_ok(dtype) || (out_dtype != dtype && out_dtype != PCV_F32))
         return fail(ctx, PCV_ERR_INVALID, "pcv_avgpool2d_pad: bad argument (C must be a multiple of 8, pad <= k/2)");
@@ -2049,11 +2010,7 @@ int pcv_avgpool2d_pad(pcv_ctx* ctx, const void* x, void* y, int N, int H, int W,
     if (Ho <= 0 || Wo <= 0) return fail(ctx, PCV_ERR_INVALID, "pcv_avgpool2d_pad: empty output");
     hipStream_t st = (hipStream_t)stream;
     const int cp = count_include_pad ? 1 : 0;
-    if (dtype == PCV_BF16) launch_avg<PCV_BF16>(x, y, N, H, W, C, Ho, Wo, k, s, out_dtype, st, p, cp, ctx->ovf);
-    else if (dtype == PCV_F16) launch_avg<PCV_F16>(x, y, N, H, W, C, Ho, Wo, k, s, out_dtype, st, p, cp, ctx->ovf);
-    else launch_avg<PCV_F32>(x, y, N, H, W, C, Ho, Wo, k, s, out_dtype, st, p, cp, ctx->ovf);
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    return launch_avg(ctx, "pcv_avgpool2d_pad", x, y, N, H, W, C, Ho, Wo, k, s, dtype, out_dtype, st, p, cp, ctx->ovf);
 }
 
 int pcv_conv1x1_pair_supported(const pcv_conv_desc* d1, const pcv_conv_desc* d2) {
@@ -2091,8 +2048,7 @@ int pcv_conv1x1_pair_gated_fused(pcv_ctx* ctx, const pcv_conv_desc* d1, const pc
 static int pair_impl(pcv_ctx* ctx, const pcv_conv_desc* d1, const pcv_conv_desc* d2, const void* x, const void* packed1,
                      const float* scale1, const float* shift1, const float* gate, const void* residual, void* y1,
                      const void* packed2, const float* scale2, const float* shift2, void* y2, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!d1 || !d2 || !x || !packed1 || !scale1 || !shift1 || !residual || !y1 || !packed2 || !scale2 || !shift2 || !y2)
         return fail(ctx, PCV_ERR_INVALID, "pcv_conv1x1_pair_fused: NULL argument");
     if (const char* why = pair_unsupported(*d1, *d2)) return fail(ctx, PCV_ERR_INVALID, std::string("pcv_conv1x1_pair_fused: ") + why);
@@ -2164,8 +2120,7 @@ int pcv_conv1x1_pair_idconv_fused(pcv_ctx* ctx, const pcv_conv_desc* d_id, const
                                   const void* x0, const void* packed_id, const float* scale_id, const float* shift_id,
                                   const void* x, const void* packed1, const float* scale1, const float* shift1, void* y1,
                                   const void* packed2, const float* scale2, const float* shift2, void* y2, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!d_id || !d1 || !d2 || !x0 || !packed_id || !scale_id || !shift_id || !x || !packed1 || !scale1 || !shift1 || !y1 ||
         !packed2 || !scale2 || !shift2 || !y2)
         return fail(ctx, PCV_ERR_INVALID, "pcv_conv1x1_pair_idconv_fused: NULL argument");
@@ -2200,85 +2155,69 @@ int pcv_conv1x1_pair_idconv_fused(pcv_ctx* ctx, const pcv_conv_desc* d_id, const
 
 int pcv_channel_slice(pcv_ctx* ctx, const void* x, void* y, long rows, int C, int offset, int x_cpitch, int y_cpitch, int dtype,
                       void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!x || !y || rows <= 0 || C <= 0 || offset < 0 || x_cpitch < offset + C || y_cpitch < C || y_cpitch % 8 != 0 || !dtype_ok(dtype))
         return fail(ctx, PCV_ERR_INVALID, "pcv_channel_slice: bad argument (y_cpitch must be a multiple of 8 and hold C channels)");
-    const long total = rows * (y_cpitch / 8);
-    const unsigned grid = (unsigned)((total + 255) / 256);
+    unsigned grid = 0;
+    if (int rc = flat_grid(ctx, "pcv_channel_slice", (long long)rows * (y_cpitch / 8), &grid)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == PCV_BF16) channel_slice_kernel<PCV_BF16><<<grid, 256, 0, st>>>(x, y, rows, C, offset, x_cpitch, y_cpitch);
-    else if (dtype == PCV_F16) channel_slice_kernel<PCV_F16><<<grid, 256, 0, st>>>(x, y, rows, C, offset, x_cpitch, y_cpitch);
-    else channel_slice_kernel<PCV_F32><<<grid, 256, 0, st>>>(x, y, rows, C, offset, x_cpitch, y_cpitch);
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    for_dtype(dtype, [&](auto T) { channel_slice_kernel<DT_OF(T)><<<grid, 256, 0, st>>>(x, y, rows, C, offset, x_cpitch, y_cpitch); });
+    return launched(ctx);
 }
 
 int pcv_channel_concat(pcv_ctx* ctx, const void* x, void* y, long rows, int C, int x_cpitch, int y_cpitch, int y_offset, int dtype,
                        void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!x || !y || rows <= 0 || C <= 0 || C % 8 != 0 || x_cpitch < C || x_cpitch % 8 != 0 || y_offset < 0 || y_offset % 8 != 0 ||
         y_cpitch < y_offset + C || y_cpitch % 8 != 0 || !dtype_ok(dtype) || !aligned16(x) || !aligned16(y))
         return fail(ctx, PCV_ERR_INVALID, "pcv_channel_concat: bad argument (C, offset and pitches must be multiples of 8, y must hold the slice)");
-    const long total = rows * (C / 8);
-    const unsigned grid = (unsigned)((total + 255) / 256);
+    unsigned grid = 0;
+    if (int rc = flat_grid(ctx, "pcv_channel_concat", (long long)rows * (C / 8), &grid)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == PCV_BF16) channel_concat_kernel<PCV_BF16><<<grid, 256, 0, st>>>(x, y, rows, C, x_cpitch, y_cpitch, y_offset);
-    else if (dtype == PCV_F16) channel_concat_kernel<PCV_F16><<<grid, 256, 0, st>>>(x, y, rows, C, x_cpitch, y_cpitch, y_offset);
-    else channel_concat_kernel<PCV_F32><<<grid, 256, 0, st>>>(x, y, rows, C, x_cpitch, y_cpitch, y_offset);
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    for_dtype(dtype, [&](auto T) { channel_concat_kernel<DT_OF(T)><<<grid, 256, 0, st>>>(x, y, rows, C, x_cpitch, y_cpitch, y_offset); });
+    return launched(ctx);
 }
 
 int pcv_interpolate(pcv_ctx* ctx, const void* x, void* y, int N, int H, int W, int C, int Ho, int Wo, int bilinear,
                     int align_corners, int dtype, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!x || !y || N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 != 0 || Ho <= 0 || Wo <= 0 || !dtype_ok(dtype))
         return fail(ctx, PCV_ERR_INVALID, "pcv_interpolate: bad argument (C must be a multiple of 8)");
-    const long total = (long)N * Ho * Wo * (C / 8);
-    const unsigned grid = (unsigned)((total + 255) / 256);
+    unsigned grid = 0;
+    if (int rc = flat_grid(ctx, "pcv_interpolate", (long long)N * Ho * Wo * (C / 8), &grid)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == PCV_BF16) interpolate_kernel<PCV_BF16><<<grid, 256, 0, st>>>(x, y, N, H, W, C, Ho, Wo, bilinear, align_corners);
-    else if (dtype == PCV_F16) interpolate_kernel<PCV_F16><<<grid, 256, 0, st>>>(x, y, N, H, W, C, Ho, Wo, bilinear, align_corners);
-    else interpolate_kernel<PCV_F32><<<grid, 256, 0, st>>>(x, y, N, H, W, C, Ho, Wo, bilinear, align_corners);
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    for_dtype(dtype, [&](auto T) { interpolate_kernel<DT_OF(T)><<<grid, 256, 0, st>>>(x, y, N, H, W, C, Ho, Wo, bilinear, align_corners); });
+    return launched(ctx);
 }
 
 int pcv_channel_interleave2(pcv_ctx* ctx, const void* a, const void* b, void* y, long rows, int Ch, int a_cpitch, int b_cpitch,
                             int y_cpitch, int dtype, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!a || !b || !y || rows <= 0 || Ch <= 0 || a_cpitch < Ch || b_cpitch < Ch || y_cpitch < 2 * Ch || y_cpitch % 8 != 0 ||
         !dtype_ok(dtype))
         return fail(ctx, PCV_ERR_INVALID, "pcv_channel_interleave2: bad argument (y_cpitch must be a multiple of 8 and hold 2*Ch channels)");
-    const long total = rows * (y_cpitch / 8);
-    const unsigned grid = (unsigned)((total + 255) / 256);
+    unsigned grid = 0;
+    if (int rc = flat_grid(ctx, "pcv_channel_interleave2", (long long)rows * (y_cpitch / 8), &grid)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == PCV_BF16) channel_interleave2_kernel<PCV_BF16><<<grid, 256, 0, st>>>(a, b, y, rows, Ch, a_cpitch, b_cpitch, y_cpitch);
-    else if (dtype == PCV_F16) channel_interleave2_kernel<PCV_F16><<<grid, 256, 0, st>>>(a, b, y, rows, Ch, a_cpitch, b_cpitch, y_cpitch);
-    else channel_interleave2_kernel<PCV_F32><<<grid, 256, 0, st>>>(a, b, y, rows, Ch, a_cpitch, b_cpitch, y_cpitch);
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    for_dtype(dtype, [&](auto T) {
+        channel_interleave2_kernel<DT_OF(T)><<<grid, 256, 0, st>>>(a, b, y, rows, Ch, a_cpitch, b_cpitch, y_cpitch);
+    });
+    return launched(ctx);
 }
 
 int pcv_preprocess_u8(pcv_ctx* ctx, const unsigned char* x, void* y, int N, int Hs, int Ws, int C, int top, int left, int H,
                       int W, int wpitch, const float* mean, const float* inv_std, int dtype, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!x || !y || !mean || !inv_std || N <= 0 || Hs <= 0 || Ws <= 0 || C <= 0 || C > 4 || H <= 0 || W <= 0 || top < 0 ||
         left < 0 || top + H > Hs || left + W > Ws || wpitch < W || !dtype_ok(dtype))
         return fail(ctx, PCV_ERR_INVALID, "pcv_preprocess_u8: bad argument (C <= 4, crop inside the frame, wpitch >= W)");
-    const long total = (long)N * H * wpitch;
-    const unsigned grid = (unsigned)((total + 255) / 256);
+    unsigned grid = 0;
+    if (int rc = flat_grid(ctx, "pcv_preprocess_u8", (long long)N * H * wpitch, &grid)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == PCV_BF16) preprocess_u8_kernel<PCV_BF16><<<grid, 256, 0, st>>>(x, y, N, Hs, Ws, C, top, left, H, W, 4, wpitch, mean, inv_std, ctx->ovf);
-    else if (dtype == PCV_F16) preprocess_u8_kernel<PCV_F16><<<grid, 256, 0, st>>>(x, y, N, Hs, Ws, C, top, left, H, W, 4, wpitch, mean, inv_std, ctx->ovf);
-    else preprocess_u8_kernel<PCV_F32><<<grid, 256, 0, st>>>(x, y, N, Hs, Ws, C, top, left, H, W, 4, wpitch, mean, inv_std, ctx->ovf);
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    for_dtype(dtype, [&](auto T) {
+        preprocess_u8_kernel<DT_OF(T)><<<grid, 256, 0, st>>>(x, y, N, Hs, Ws, C, top, left, H, W, 4, wpitch, mean, inv_std, ctx->ovf);
+    });
+    return launched(ctx);
 }
 
 // Resize + crop + normalise of ragged frames (resize_plan.hpp, resize_kernel.hpp). The two planning calls are host arithmetic only:
@@ -2300,8 +2239,7 @@ int pcv_resize_plan(const void* const* frames, int N, const int* hs, const int* 
 
 int pcv_resize_crop_u8(pcv_ctx* ctx, const void* plan_host, const void* plan_dev, size_t bytes, void* y, int wpitch,
                        const float* mean, const float* inv_std, int dtype, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!plan_host || !plan_dev || !y || !mean || !inv_std || !dtype_ok(dtype) || !aligned16(plan_dev) || !aligned16(y))
         return fail(ctx, PCV_ERR_INVALID, "pcv_resize_crop_u8: bad argument (NULL pointer, dtype, or plan_dev / y not 16-byte aligned)");
     if (const char* why = pcv_resize::validate(plan_host, bytes)) return fail(ctx, PCV_ERR_INVALID, std::string("pcv_resize_crop_u8: ") + why);
@@ -2309,22 +2247,17 @@ int pcv_resize_crop_u8(pcv_ctx* ctx, const void* plan_host, const void* plan_dev
     std::memcpy(&hd, plan_host, sizeof(hd));
     if (wpitch < hd.W) return fail(ctx, PCV_ERR_INVALID, "pcv_resize_crop_u8: wpitch < W");
     if (!in_window((unsigned long long)hd.N * hd.H * wpitch * 4 * esize(dtype))) return too_large(ctx, "pcv_resize_crop_u8", "y");
-    int blocks = hd.items;                                                  // a fresh block per (frame, band): see resize_kernel.hpp
-    if (ctx->max_blocks > 0 && blocks > ctx->max_blocks) blocks = ctx->max_blocks;      // multi-round tests only (as pcv_se_scale)
+    const unsigned blocks = (unsigned)cap_blocks(ctx, hd.items);            // a fresh block per (frame, band): see resize_kernel.hpp
     const char* pd = static_cast<const char*>(plan_dev);
     hipStream_t st = (hipStream_t)stream;
     const unsigned lds = (unsigned)hd.stage_bytes;
-    if (dtype == PCV_BF16) resize_crop_u8_kernel<PCV_BF16><<<blocks, 256, lds, st>>>(pd, y, wpitch, mean, inv_std, ctx->ovf);
-    else if (dtype == PCV_F16) resize_crop_u8_kernel<PCV_F16><<<blocks, 256, lds, st>>>(pd, y, wpitch, mean, inv_std, ctx->ovf);
-    else resize_crop_u8_kernel<PCV_F32><<<blocks, 256, lds, st>>>(pd, y, wpitch, mean, inv_std, ctx->ovf);
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    for_dtype(dtype, [&](auto T) { resize_crop_u8_kernel<DT_OF(T)><<<blocks, 256, lds, st>>>(pd, y, wpitch, mean, inv_std, ctx->ovf); });
+    return launched(ctx);
 }
 
 int pcv_classify_f32(pcv_ctx* ctx, const float* logits, int N, int J, int k, int* top_idx, float* top_val, float* top_prob,
                      const long long* labels, int* rank, float* nll, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!logits) return fail(ctx, PCV_ERR_INVALID, "pcv_classify_f32: logits is NULL");
     if (N < 1) return fail(ctx, PCV_ERR_INVALID, "pcv_classify_f32: N = " + std::to_string(N) + " is outside the limit N >= 1");
     if (J < 1 || J > kClassifyMaxJ)
@@ -2334,8 +2267,7 @@ int pcv_classify_f32(pcv_ctx* ctx, const float* logits, int N, int J, int k, int
     if (k == 0 && (top_idx || top_val || top_prob))
         return fail(ctx, PCV_ERR_INVALID, "pcv_classify_f32: k = 0 is allowed only when top_idx, top_val and top_prob are all NULL");
     if ((rank || nll) && !labels) return fail(ctx, PCV_ERR_INVALID, "pcv_classify_f32: rank and nll need labels");
-    long long blocks = N;
-    if (ctx->max_blocks > 0 && blocks > ctx->max_blocks) blocks = ctx->max_blocks;      // multi-round tests only (as pcv_se_scale)
+    const long long blocks = cap_blocks(ctx, N);
     const Kernel K = classify_kernel_of(J);
     void* args[] = {&logits, &N, &J, &k, &top_idx, &top_val, &top_prob, &labels, &rank, &nll};
     HIP_TRY(ctx, hipLaunchKernel(K.fn, dim3((unsigned)blocks), dim3((unsigned)K.threads), args, (size_t)K.lds, (hipStream_t)stream));
@@ -2350,8 +2282,7 @@ int pcv_mbconv_fused(pcv_ctx* ctx, const pcv_conv_desc* d_exp, const pcv_conv_de
                      const void* x, const void* packed_exp, const float* scale_e, const float* shift_e, const void* packed_dw,
                      const float* scale_d, const float* shift_d, const void* packed_proj, const float* scale_p,
                      const float* shift_p, const void* residual, void* y, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (!d_dw || !d_proj || !x || !packed_dw || !scale_d || !shift_d || !packed_proj || !scale_p || !shift_p || !y ||
         (d_exp && (!packed_exp || !scale_e || !shift_e)))
         return fail(ctx, PCV_ERR_INVALID, "pcv_mbconv_fused: NULL argument");
@@ -2442,21 +2373,17 @@ int pcv_mbconv_fused(pcv_ctx* ctx, const pcv_conv_desc* d_exp, const pcv_conv_de
 
 int pcv_bn_act(pcv_ctx* ctx, const void* x, const float* scale, const float* shift, void* y, long rows, int C, int x_cpitch,
                int act, int dtype, void* stream) {
-    if (!ctx) return PCV_ERR_INVALID;
-    DeviceGuard device_guard(ctx->device);
+    PCV_ENTER(ctx);
     if (x_cpitch <= 0) x_cpitch = C;
     if (!x || !scale || !shift || !y || rows <= 0 || C <= 0 || C % 8 != 0 || x_cpitch < C || x_cpitch % 8 != 0 || !dtype_ok(dtype) ||
         act < 0 || act > PCV_ACT_HSWISH)
         return fail(ctx, PCV_ERR_INVALID, "pcv_bn_act: bad argument (C and x_cpitch must be multiples of 8, x_cpitch >= C)");
     const long total8 = rows * (C / 8);
-    long blocks = (total8 + 255) / 256;
-    if (ctx->max_blocks > 0 && blocks > ctx->max_blocks) blocks = ctx->max_blocks;       // (see pcv_se_scale)
+    unsigned blocks = 0;
+    if (int rc = stream_grid(ctx, "pcv_bn_act", total8, &blocks)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == PCV_BF16) bn_act_kernel<PCV_BF16><<<(unsigned)blocks, 256, 0, st>>>(x, scale, shift, y, total8, C, x_cpitch, act, ctx->ovf);
-    else if (dtype == PCV_F16) bn_act_kernel<PCV_F16><<<(unsigned)blocks, 256, 0, st>>>(x, scale, shift, y, total8, C, x_cpitch, act, ctx->ovf);
-    else bn_act_kernel<PCV_F32><<<(unsigned)blocks, 256, 0, st>>>(x, scale, shift, y, total8, C, x_cpitch, act, ctx->ovf);
-    HIP_TRY(ctx, hipGetLastError());
-    return PCV_OK;
+    for_dtype(dtype, [&](auto T) { bn_act_kernel<DT_OF(T)><<<blocks, 256, 0, st>>>(x, scale, shift, y, total8, C, x_cpitch, act, ctx->ovf); });
+    return launched(ctx);
 }
 
 }  // extern "C"

@@ -5,7 +5,7 @@
 """
 
 __all__ = ['NHWC', 'DTYPES', 'default_dtype', 'set_compute_dtype', 'compute_dtype_of', 'Fp16Guard', 'fp16_overflow_count', 'from_nchw', 'to_nchw', 'ConvRunner',
-           'BnActRunner', 'maxpool2d', 'avgpool2d', 'avgpool2d_pad', 'global_avgpool', 'se_forward', 'splat_forward', 'cbam_forward', 'channel_slice', 'cat_shuffle2', 'act_code',
+           'BnActRunner', 'maxpool2d', 'avgpool2d', 'avgpool2d_pad', 'global_avgpool', 'se_excite', 'se_scale', 'se_forward', 'splat_forward', 'cbam_channel_gate', 'cbam_spatial', 'cbam_forward', 'channel_slice', 'cat_shuffle2', 'act_code',
            'boundary', 'round8', 'channel_concat_into', 'interpolate', 'add', 'classify']
 
 import os
@@ -74,23 +74,20 @@ class Fp16Guard(object):
         self.device = device
         if torch_dtype == torch.float16:
             self.slot = torch.empty(1, dtype=torch.int32, device=device)
-            ctx = _ctx(device)
-            _lib.check(_lib.lib().pcv_fp16_guard_begin(ctx, _ptr(self.slot), _stream(device)), ctx)
+            _call(device, "fp16_guard_begin", _ptr(self.slot))
 
     def finish(self, y: torch.Tensor) -> torch.Tensor:
         if self.slot is not None:
             if y.dtype != torch.float32 or not y.is_contiguous():
                 raise RuntimeError("the fp16 guard poisons a contiguous fp32 result")
-            ctx = _ctx(self.device)
-            _lib.check(_lib.lib().pcv_fp16_guard_end(ctx, _ptr(self.slot), _ptr(y), y.numel(), _stream(self.device)), ctx)
+            _call(self.device, "fp16_guard_end", _ptr(self.slot), _ptr(y), y.numel())
         return y
 
 
 def fp16_overflow_count(device) -> int:
     """How many threads of this device's context have rounded a value beyond fp16's range so far (synchronises the stream)."""
-    ctx = _ctx(device)
     n = ctypes.c_uint(0)
-    _lib.check(_lib.lib().pcv_fp16_overflow_count(ctx, ctypes.byref(n), _stream(device)), ctx)
+    _call(device, "fp16_overflow_count", ctypes.byref(n))
     return int(n.value)
 
 
@@ -138,20 +135,51 @@ class _ShapeOnly(object):
         self.N, self.H, self.W, self.C, self.dtype, self.wpitch, self.cpitch = N, H, W, C, dtype, W, round8(C)
 
 
-def _stream(device) -> ctypes.c_void_p:
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _ctx(device):
+def _device_index(device) -> int:
     if device.type != "cuda":
         raise RuntimeError("pytorchcv_amd runs on MI355X (gfx950) only: got a tensor on '{}'. Move the model and the input "
                            "to a CUDA/HIP device; there is no CPU path in this package.".format(device))
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    return _lib.ctx_for(idx)
+    return device.index if device.index is not None else torch.cuda.current_device()
+
+
+# the current stream's handle without building a torch.cuda.Stream around it: a forward at batch 1 is bound by this host code, and
+# every launch asks for the stream
+_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None) or (lambda idx: torch.cuda.current_stream(idx).cuda_stream)
+
+
+def _stream(device) -> ctypes.c_void_p:
+    return ctypes.c_void_p(_raw_stream(_device_index(device)))
+
+
+def _ctx(device):
+    return _lib.ctx_for(_device_index(device))
 
 
 def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _call(device, name, *args, accept=()):
+    """pcv_<name>(ctx, *args, stream) on `device`'s context and current stream. A non-zero code raises PcvError with the library's
+    text, unless it is one of `accept`: those are returned for the caller to handle."""
+    ctx = _ctx(device)
+    rc = getattr(_lib.lib(), "pcv_" + name)(ctx, *args, _stream(device))
+    if rc != 0 and rc not in accept:
+        _lib.check(rc, ctx)
+    return rc
+
+
+def _conv_out(d: ConvDesc, H: int, W: int):
+    """(Ho, Wo) of the convolution `d` on an H x W map."""
+    return ((H + d.pad_t + d.pad_b - d.dil_h * (d.kh - 1) - 1) // d.stride_h + 1,
+            (W + d.pad_l + d.pad_r - d.dil_w * (d.kw - 1) - 1) // d.stride_w + 1)
+
+
+def _require_eval(*runners):
+    """BatchNorm is folded into the packed state: a runner (None entries are skipped) whose BatchNorm is in training mode is refused."""
+    for r in runners:
+        if r is not None and r.bn is not None and r.bn.training:
+            raise RuntimeError("pytorchcv_amd is an inference path: call net.eval() first (BatchNorm is folded)")
 
 
 class LazyNCHW(NHWC):
@@ -206,8 +234,7 @@ def from_nchw(x: torch.Tensor, dtype: str, stem: bool = True) -> NHWC:
     else:
         cp, wp = (C + 7) // 8 * 8, W
     y = torch.empty((N, H, wp, cp), dtype=tdt, device=x.device)
-    ctx = _ctx(x.device)
-    _lib.check(_lib.lib().pcv_nchw_to_nhwc(ctx, _ptr(x), _ptr(y), N, C, H, W, cp, wp, code, _stream(x.device)), ctx)
+    _call(x.device, "nchw_to_nhwc", _ptr(x), _ptr(y), N, C, H, W, cp, wp, code)
     return NHWC(y, N, H, W, C, wpitch=wp, cpitch=cp)
 
 
@@ -216,9 +243,7 @@ def to_nchw(a: NHWC) -> torch.Tensor:
     if a.wpitch != a.W:
         raise RuntimeError("cannot convert a row-padded input handle back to NCHW")
     y = torch.empty((a.N, a.C, a.H, a.W), dtype=torch.float32, device=a.device)
-    ctx = _ctx(a.device)
-    _lib.check(_lib.lib().pcv_nhwc_to_nchw(ctx, _ptr(a.t), _ptr(y), a.N, a.C, a.H, a.W, a.cpitch, _CODE_OF_TORCH[a.dtype],
-                                           _stream(a.device)), ctx)
+    _call(a.device, "nhwc_to_nchw", _ptr(a.t), _ptr(y), a.N, a.C, a.H, a.W, a.cpitch, _CODE_OF_TORCH[a.dtype])
     return y
 
 
@@ -342,7 +367,7 @@ class ConvRunner(object):
         w = self.conv.weight
         if w.device != dev:
             raise RuntimeError("model parameters are on {} but the input is on {}".format(w.device, dev))
-        L, ctx, st = _lib.lib(), _ctx(dev), _stream(dev)
+        L = _lib.lib()
         nbytes = ctypes.c_size_t(0)
         fn_bytes = L.pcv_dwconv_packed_bytes if self.depthwise else L.pcv_conv_packed_bytes
         if fn_bytes(ctypes.byref(d), ctypes.byref(nbytes)) != 0:
@@ -357,8 +382,7 @@ class ConvRunner(object):
         if w32.shape[0] != C or w32.shape[1] != cin_g:              # zero rows / columns for the pad channels
             w32 = F.pad(w32, (0, 0, 0, 0, 0, cin_g - w32.shape[1], 0, C - w32.shape[0]))
         w32 = w32.contiguous()
-        fn_pack = L.pcv_dwconv_pack if self.depthwise else L.pcv_conv_pack
-        _lib.check(fn_pack(ctx, ctypes.byref(d), _ptr(w32), _ptr(packed), st), ctx)
+        _call(dev, "dwconv_pack" if self.depthwise else "conv_pack", ctypes.byref(d), _ptr(w32), _ptr(packed))
 
         def padded(t, fill):
             t = t.detach().float()
@@ -374,11 +398,9 @@ class ConvRunner(object):
             b = padded(self.bn.bias, 0.0) if self.bn.bias is not None else torch.zeros(C, device=dev)
             m = padded(self.bn.running_mean, 0.0)
             v = padded(self.bn.running_var, 1.0)
-            _lib.check(L.pcv_bn_fold(ctx, C, _ptr(g), _ptr(b), _ptr(m), _ptr(v), ctypes.c_float(self.bn.eps), _ptr(bias),
-                                     _ptr(scale), _ptr(shift), st), ctx)
+            _call(dev, "bn_fold", C, _ptr(g), _ptr(b), _ptr(m), _ptr(v), ctypes.c_float(self.bn.eps), _ptr(bias), _ptr(scale), _ptr(shift))
         else:
-            _lib.check(L.pcv_bn_fold(ctx, C, None, None, None, None, ctypes.c_float(0.0), _ptr(bias), _ptr(scale),
-                                     _ptr(shift), st), ctx)
+            _call(dev, "bn_fold", C, None, None, None, None, ctypes.c_float(0.0), _ptr(bias), _ptr(scale), _ptr(shift))
         torch.cuda.current_stream(dev).synchronize()      # w32 & friends are temporaries; load-time only
         self.packed, self.scale, self.shift, self._key = packed, scale, shift, key
 
@@ -396,8 +418,7 @@ class ConvRunner(object):
     def run(self, x: NHWC, act=0, residual: NHWC | None = None, post_act=0, out_fp32=False, pad4=None, out=None, gate=None) -> NHWC:
         """`pad4`: explicit (left, right, top, bottom) zero padding for this call (the `F.pad` a unit applies in front of
         a padding-0 convolution, efficientnet.py:108-109,189-190,236-237); it stays inside the kernel's bounds checks."""
-        if self.bn is not None and self.bn.training:
-            raise RuntimeError("pytorchcv_amd is an inference path: call net.eval() first (BatchNorm is folded)")
+        _require_eval(self)
         if isinstance(x, LazyNCHW) and not x.materialized and residual is None and out is None and gate is None and not out_fp32 \
                 and post_act == 0 and pad4 is None:
             y = self._stem_from_nchw(x, act, pool=False)
@@ -413,19 +434,17 @@ class ConvRunner(object):
         if self.depthwise or self.pad4 is not None or x.src.numel() * 4 >= (1 << 31):      # (one launch addresses < 2 GiB: the
             return None                                                                      # converted path splits the batch)
         d = self.desc(x, act, 0, False)
-        L, ctx = _lib.lib(), _ctx(x.device)
-        if not L.pcv_conv2d_nchw_stem_supported(ctypes.byref(d), 1 if pool else 0):
+        if not _lib.lib().pcv_conv2d_nchw_stem_supported(ctypes.byref(d), 1 if pool else 0):
             return None
         self.prepare(x, d)
-        Ho = (x.H + d.pad_t + d.pad_b - d.dil_h * (d.kh - 1) - 1) // d.stride_h + 1
-        Wo = (x.W + d.pad_l + d.pad_r - d.dil_w * (d.kw - 1) - 1) // d.stride_w + 1
+        Ho, Wo = _conv_out(d, x.H, x.W)
         if pool:
             Ho, Wo = (Ho + 2 - 3) // 2 + 1, (Wo + 2 - 3) // 2 + 1
         if Ho <= 0 or Wo <= 0:
             return None
         y = torch.empty((x.N, Ho, Wo, d.Cout), dtype=x.dtype, device=x.device)
-        _lib.check(L.pcv_conv2d_nchw_stem_fused(ctx, ctypes.byref(d), _ptr(x.src), _ptr(self.packed), _ptr(self.scale), _ptr(self.shift),
-                                                _ptr(y), 1 if pool else 0, _stream(x.device)), ctx)
+        _call(x.device, "conv2d_nchw_stem_fused", ctypes.byref(d), _ptr(x.src), _ptr(self.packed), _ptr(self.scale), _ptr(self.shift),
+              _ptr(y), 1 if pool else 0)
         return NHWC(y, x.N, Ho, Wo, self.conv.out_channels, cpitch=d.Cout)
 
     def run_maxpool(self, x: NHWC, act: int, k: int, s: int, p: int, ceil_mode: bool = False):
@@ -433,25 +452,22 @@ class ConvRunner(object):
         (pcv_conv2d_maxpool_fused: the stem convolution with MaxPool2d(3, 2, 1)); returns the pooled handle or None."""
         if not FUSE_UNITS or self.depthwise or self.pad4 is not None:
             return None
-        if self.bn is not None and self.bn.training:
-            raise RuntimeError("pytorchcv_amd is an inference path: call net.eval() first (BatchNorm is folded)")
+        _require_eval(self)
         if isinstance(x, LazyNCHW) and not x.materialized and (k, s, p) == (3, 2, 1) and not ceil_mode:
             y = self._stem_from_nchw(x, act, pool=True)
             if y is not None:
                 return y
         d = self.desc(x, act, 0, False)
-        L, ctx = _lib.lib(), _ctx(x.device)
-        if not L.pcv_conv2d_maxpool_supported(ctypes.byref(d), k, s, p, 1 if ceil_mode else 0):
+        if not _lib.lib().pcv_conv2d_maxpool_supported(ctypes.byref(d), k, s, p, 1 if ceil_mode else 0):
             return None
         self.prepare(x, d)
-        Ho = (x.H + d.pad_t + d.pad_b - d.dil_h * (d.kh - 1) - 1) // d.stride_h + 1
-        Wo = (x.W + d.pad_l + d.pad_r - d.dil_w * (d.kw - 1) - 1) // d.stride_w + 1
+        Ho, Wo = _conv_out(d, x.H, x.W)
         Hq, Wq = (Ho + 2 * p - k) // s + 1, (Wo + 2 * p - k) // s + 1
         if Hq <= 0 or Wq <= 0:
             return None
         y = torch.empty((x.N, Hq, Wq, d.Cout), dtype=x.dtype, device=x.device)
-        _lib.check(L.pcv_conv2d_maxpool_fused(ctx, ctypes.byref(d), _ptr(x.t), _ptr(self.packed), _ptr(self.scale), _ptr(self.shift),
-                                              _ptr(y), k, s, p, 1 if ceil_mode else 0, _stream(x.device)), ctx)
+        _call(x.device, "conv2d_maxpool_fused", ctypes.byref(d), _ptr(x.t), _ptr(self.packed), _ptr(self.scale), _ptr(self.shift),
+              _ptr(y), k, s, p, 1 if ceil_mode else 0)
         return NHWC(y, x.N, Hq, Wq, self.conv.out_channels, cpitch=d.Cout)
 
     def run_pair(self, x: NHWC, residual: NHWC, act: int, post_act: int, nxt: "ConvRunner", nxt_act: int, gate=None):
@@ -459,10 +475,9 @@ class ConvRunner(object):
         (pcv_conv1x1_pair_fused): returns (y1, y2), or None when the pair of shapes is not covered by the fused kernel."""
         if not FUSE_UNITS or residual is None or self.depthwise or nxt.depthwise or self.pad4 is not None or nxt.pad4 is not None:
             return None
-        if (self.bn is not None and self.bn.training) or (nxt.bn is not None and nxt.bn.training):
-            raise RuntimeError("pytorchcv_amd is an inference path: call net.eval() first (BatchNorm is folded)")
+        _require_eval(self, nxt)
         c = self.conv
-        L, ctx, st = _lib.lib(), _ctx(x.device), _stream(x.device)
+        L = _lib.lib()
         d1 = self.desc(x, act, post_act, True)
         d2 = nxt.desc(_ShapeOnly(x.N, x.H, x.W, c.out_channels, x.dtype), nxt_act, 0, False)
         supported = L.pcv_conv1x1_pair_gated_supported if gate is not None else L.pcv_conv1x1_pair_supported
@@ -477,14 +492,12 @@ class ConvRunner(object):
         y1 = NHWC(t1, x.N, x.H, x.W, c.out_channels, cpitch=d1.Cout)
         self.prepare(x, d1)
         nxt.prepare(y1, d2)
+        first = (ctypes.byref(d1), ctypes.byref(d2), _ptr(x.t), _ptr(self.packed), _ptr(self.scale), _ptr(self.shift))
+        second = (_ptr(residual.t), _ptr(t1), _ptr(nxt.packed), _ptr(nxt.scale), _ptr(nxt.shift), _ptr(t2))
         if gate is not None:
-            _lib.check(L.pcv_conv1x1_pair_gated_fused(ctx, ctypes.byref(d1), ctypes.byref(d2), _ptr(x.t), _ptr(self.packed),
-                                                      _ptr(self.scale), _ptr(self.shift), _ptr(gate), _ptr(residual.t), _ptr(t1),
-                                                      _ptr(nxt.packed), _ptr(nxt.scale), _ptr(nxt.shift), _ptr(t2), st), ctx)
+            _call(x.device, "conv1x1_pair_gated_fused", *first, _ptr(gate), *second)
         else:
-            _lib.check(L.pcv_conv1x1_pair_fused(ctx, ctypes.byref(d1), ctypes.byref(d2), _ptr(x.t), _ptr(self.packed),
-                                                _ptr(self.scale), _ptr(self.shift), _ptr(residual.t), _ptr(t1), _ptr(nxt.packed),
-                                                _ptr(nxt.scale), _ptr(nxt.shift), _ptr(t2), st), ctx)
+            _call(x.device, "conv1x1_pair_fused", *first, *second)
         return y1, NHWC(t2, x.N, x.H, x.W, nxt.conv.out_channels, cpitch=d2.Cout)
 
     def run_pair_idconv(self, x: NHWC, x0: NHWC, idr: "ConvRunner", act: int, post_act: int, nxt: "ConvRunner", nxt_act: int):
@@ -493,16 +506,14 @@ class ConvRunner(object):
         (pcv_conv1x1_pair_idconv_fused). Returns (y1, y2), or None when the shapes are not covered."""
         if not FUSE_UNITS or any(r.depthwise or r.pad4 is not None for r in (self, idr, nxt)):
             return None
-        if any(r.bn is not None and r.bn.training for r in (self, idr, nxt)):
-            raise RuntimeError("pytorchcv_amd is an inference path: call net.eval() first (BatchNorm is folded)")
+        _require_eval(self, idr, nxt)
         if not x0.dense or x0.dtype != x.dtype or (x0.N, x0.H, x0.W) != (x.N, x.H, x.W):
             return None
         c = self.conv
-        L, ctx, st = _lib.lib(), _ctx(x.device), _stream(x.device)
         di = idr.desc(x0, 0, 0, False)
         d1 = self.desc(x, act, post_act, True)
         d2 = nxt.desc(_ShapeOnly(x.N, x.H, x.W, c.out_channels, x.dtype), nxt_act, 0, False)
-        if not L.pcv_conv1x1_pair_idconv_supported(ctypes.byref(di), ctypes.byref(d1), ctypes.byref(d2)):
+        if not _lib.lib().pcv_conv1x1_pair_idconv_supported(ctypes.byref(di), ctypes.byref(d1), ctypes.byref(d2)):
             return None
         t1 = torch.empty((x.N, x.H, x.W, d1.Cout), dtype=x.dtype, device=x.device)
         t2 = torch.empty((x.N, x.H, x.W, d2.Cout), dtype=x.dtype, device=x.device)
@@ -510,19 +521,16 @@ class ConvRunner(object):
         idr.prepare(x0, di)
         self.prepare(x, d1)
         nxt.prepare(y1, d2)
-        _lib.check(L.pcv_conv1x1_pair_idconv_fused(ctx, ctypes.byref(di), ctypes.byref(d1), ctypes.byref(d2), _ptr(x0.t),
-                                                   _ptr(idr.packed), _ptr(idr.scale), _ptr(idr.shift), _ptr(x.t), _ptr(self.packed),
-                                                   _ptr(self.scale), _ptr(self.shift), _ptr(t1), _ptr(nxt.packed), _ptr(nxt.scale),
-                                                   _ptr(nxt.shift), _ptr(t2), st), ctx)
+        _call(x.device, "conv1x1_pair_idconv_fused", ctypes.byref(di), ctypes.byref(d1), ctypes.byref(d2), _ptr(x0.t), _ptr(idr.packed),
+              _ptr(idr.scale), _ptr(idr.shift), _ptr(x.t), _ptr(self.packed), _ptr(self.scale), _ptr(self.shift), _ptr(t1),
+              _ptr(nxt.packed), _ptr(nxt.scale), _ptr(nxt.shift), _ptr(t2))
         return y1, NHWC(t2, x.N, x.H, x.W, nxt.conv.out_channels, cpitch=d2.Cout)
 
     def _launch(self, x: NHWC, d: ConvDesc, residual, out=None, gate=None):
         """`out` = (tensor [N, Ho, Wo, Ctot], channel offset): write the result into that channel slice of a wider
         (concatenation) buffer instead of a fresh tensor - `torch.cat((identity, x), dim=1)` without the copy."""
         c = self.conv
-        kh, kw = d.kh, d.kw
-        Ho = (x.H + d.pad_t + d.pad_b - d.dil_h * (kh - 1) - 1) // d.stride_h + 1
-        Wo = (x.W + d.pad_l + d.pad_r - d.dil_w * (kw - 1) - 1) // d.stride_w + 1
+        Ho, Wo = _conv_out(d, x.H, x.W)
         if Ho <= 0 or Wo <= 0:
             raise RuntimeError("convolution output would be empty")
         out_dt = torch.float32 if d.out_dtype == 0 else x.dtype
@@ -547,21 +555,18 @@ class ConvRunner(object):
 
     def _launch_range(self, x, d, residual, y, n0, n1, gate=None):
         """Launch images [n0, n1); halve the range when one launch would exceed the 2 GiB addressing window."""
-        L, ctx, st = _lib.lib(), _ctx(x.device), _stream(x.device)
         d.N = n1 - n0
-        rp = _ptr(residual.t[n0:n1]) if residual is not None else None
+        args = (ctypes.byref(d), _ptr(x.t[n0:n1]), _ptr(self.packed), _ptr(self.scale), _ptr(self.shift))
+        rest = (_ptr(residual.t[n0:n1]) if residual is not None else None, _ptr(y[n0:n1]))
+        halve = (_lib.PCV_ERR_TOO_LARGE,) if n1 - n0 > 1 else ()
         if gate is not None:
-            rc = L.pcv_conv2d_gated_fused(ctx, ctypes.byref(d), _ptr(x.t[n0:n1]), _ptr(self.packed), _ptr(self.scale),
-                                          _ptr(self.shift), _ptr(gate[n0:n1]), rp, _ptr(y[n0:n1]), st)
+            rc = _call(x.device, "conv2d_gated_fused", *args, _ptr(gate[n0:n1]), *rest, accept=halve)
         else:
-            fn = L.pcv_dwconv2d_fused if self.depthwise else L.pcv_conv2d_fused
-            rc = fn(ctx, ctypes.byref(d), _ptr(x.t[n0:n1]), _ptr(self.packed), _ptr(self.scale), _ptr(self.shift), rp, _ptr(y[n0:n1]), st)
-        if rc == _lib.PCV_ERR_TOO_LARGE and n1 - n0 > 1:
+            rc = _call(x.device, "dwconv2d_fused" if self.depthwise else "conv2d_fused", *args, *rest, accept=halve)
+        if rc != 0:
             mid = (n0 + n1) // 2
             self._launch_range(x, d, residual, y, n0, mid, gate)
             self._launch_range(x, d, residual, y, mid, n1, gate)
-            return
-        _lib.check(rc, ctx)
 
     def squeezed_excite(self, z: NHWC, w1, b1, w2, b2, mid_act: int, out_act: int) -> torch.Tensor:
         """SE gate of `SEBlock(BN(conv(z)))` for a 1x1 stride-1 convolution WITHOUT activation, computed before the convolution
@@ -585,14 +590,13 @@ class ConvRunner(object):
             self._sq_w2 = F.pad(w2.float(), (0, 0, 0, CP - Cl)).contiguous()               # [CP, M]
             self._sq_b2 = F.pad(b2.float(), (0, CP - Cl)).contiguous()
             self._sq_key = key
-        L, ctx, st = _lib.lib(), _ctx(z.device), _stream(z.device)
         M = self._sq_w1.shape[0]
         mean = torch.empty((z.N, d.Cin), dtype=torch.float32, device=z.device)
-        _lib.check(L.pcv_se_squeeze(ctx, _ptr(z.t), _ptr(mean), z.N, z.H * z.W, d.Cin, _CODE_OF_TORCH[z.dtype], st), ctx)
+        _call(z.device, "se_squeeze", _ptr(z.t), _ptr(mean), z.N, z.H * z.W, d.Cin, _CODE_OF_TORCH[z.dtype])
         mid = torch.empty((z.N, M), dtype=torch.float32, device=z.device)
         gate = torch.empty((z.N, d.Cout), dtype=torch.float32, device=z.device)
-        _lib.check(L.pcv_fc_f32(ctx, _ptr(mean), _ptr(self._sq_w1), _ptr(self._sq_b1), _ptr(mid), z.N, d.Cin, M, mid_act, st), ctx)
-        _lib.check(L.pcv_fc_f32(ctx, _ptr(mid), _ptr(self._sq_w2), _ptr(self._sq_b2), _ptr(gate), z.N, M, d.Cout, out_act, st), ctx)
+        _call(z.device, "fc_f32", _ptr(mean), _ptr(self._sq_w1), _ptr(self._sq_b1), _ptr(mid), z.N, d.Cin, M, mid_act)
+        _call(z.device, "fc_f32", _ptr(mid), _ptr(self._sq_w2), _ptr(self._sq_b2), _ptr(gate), z.N, M, d.Cout, out_act)
         return gate
 
 
@@ -609,9 +613,7 @@ def channel_slice(x: NHWC, offset: int, count: int) -> NHWC:
         raise RuntimeError("bad channel slice")
     cp = round8(count)
     y = torch.empty((x.N, x.H, x.W, cp), dtype=x.dtype, device=x.device)
-    ctx = _ctx(x.device)
-    _lib.check(_lib.lib().pcv_channel_slice(ctx, _ptr(x.t), _ptr(y), x.N * x.H * x.W, count, offset, x.cpitch, cp,
-                                            _CODE_OF_TORCH[x.dtype], _stream(x.device)), ctx)
+    _call(x.device, "channel_slice", _ptr(x.t), _ptr(y), x.N * x.H * x.W, count, offset, x.cpitch, cp, _CODE_OF_TORCH[x.dtype])
     return NHWC(y, x.N, x.H, x.W, count, cpitch=cp)
 
 
@@ -621,9 +623,8 @@ def channel_concat_into(x: NHWC, buf: torch.Tensor, coff: int):
     if x.wpitch != x.W or x.C % 8 or coff % 8 or tuple(buf.shape[:3]) != (x.N, x.H, x.W) or buf.dtype != x.dtype or \
             coff + x.C > buf.shape[3] or not buf.is_contiguous():
         raise RuntimeError("channel concatenation needs channel counts / offsets that are multiples of 8 and equal maps")
-    ctx = _ctx(x.device)
-    _lib.check(_lib.lib().pcv_channel_concat(ctx, _ptr(x.t), _ptr(buf), x.N * x.H * x.W, x.C, x.cpitch, int(buf.shape[3]), coff,
-                                             _CODE_OF_TORCH[x.dtype], _stream(x.device)), ctx)
+    _call(x.device, "channel_concat", _ptr(x.t), _ptr(buf), x.N * x.H * x.W, x.C, x.cpitch, int(buf.shape[3]), coff,
+          _CODE_OF_TORCH[x.dtype])
 
 
 def interpolate(x: NHWC, out_size, bilinear: bool, align_corners: bool) -> NHWC:
@@ -632,9 +633,8 @@ def interpolate(x: NHWC, out_size, bilinear: bool, align_corners: bool) -> NHWC:
         raise RuntimeError("interpolation on a padded handle")
     Ho, Wo = int(out_size[0]), int(out_size[1])
     y = torch.empty((x.N, Ho, Wo, x.cpitch), dtype=x.dtype, device=x.device)
-    ctx = _ctx(x.device)
-    _lib.check(_lib.lib().pcv_interpolate(ctx, _ptr(x.t), _ptr(y), x.N, x.H, x.W, x.cpitch, Ho, Wo, 1 if bilinear else 0,
-                                          1 if align_corners else 0, _CODE_OF_TORCH[x.dtype], _stream(x.device)), ctx)
+    _call(x.device, "interpolate", _ptr(x.t), _ptr(y), x.N, x.H, x.W, x.cpitch, Ho, Wo, 1 if bilinear else 0,
+          1 if align_corners else 0, _CODE_OF_TORCH[x.dtype])
     return NHWC(y, x.N, Ho, Wo, x.C, cpitch=x.cpitch)
 
 
@@ -643,12 +643,7 @@ def add(a: NHWC, b: NHWC, post_act: int = 0) -> NHWC:
     end in a convolution (a convolution takes the running sum as its epilogue residual instead)."""
     if a.t.shape != b.t.shape or a.dtype != b.dtype or not a.dense:
         raise RuntimeError("add: operands do not match")
-    ones = torch.ones((a.N, a.cpitch), dtype=torch.float32, device=a.device)
-    y = torch.empty_like(a.t)
-    ctx = _ctx(a.device)
-    _lib.check(_lib.lib().pcv_se_scale(ctx, _ptr(a.t), _ptr(ones), _ptr(b.t), _ptr(y), a.N, a.H * a.W, a.cpitch, post_act,
-                                       _CODE_OF_TORCH[a.dtype], _stream(a.device)), ctx)
-    return NHWC(y, a.N, a.H, a.W, a.C, cpitch=a.cpitch)
+    return se_scale(a, torch.ones((a.N, a.cpitch), dtype=torch.float32, device=a.device), b, post_act)
 
 
 def cat_shuffle2(a: NHWC, b: NHWC, half: int) -> NHWC:
@@ -657,9 +652,8 @@ def cat_shuffle2(a: NHWC, b: NHWC, half: int) -> NHWC:
         raise RuntimeError("cat/shuffle operands do not match")
     cp = round8(2 * half)
     y = torch.empty((a.N, a.H, a.W, cp), dtype=a.dtype, device=a.device)
-    ctx = _ctx(a.device)
-    _lib.check(_lib.lib().pcv_channel_interleave2(ctx, _ptr(a.t), _ptr(b.t), _ptr(y), a.N * a.H * a.W, half, a.cpitch, b.cpitch,
-                                                  cp, _CODE_OF_TORCH[a.dtype], _stream(a.device)), ctx)
+    _call(a.device, "channel_interleave2", _ptr(a.t), _ptr(b.t), _ptr(y), a.N * a.H * a.W, half, a.cpitch, b.cpitch, cp,
+          _CODE_OF_TORCH[a.dtype])
     return NHWC(y, a.N, a.H, a.W, 2 * half, cpitch=cp)
 
 
@@ -670,9 +664,7 @@ def maxpool2d(x: NHWC, k: int, s: int, p: int, ceil_mode: bool = False) -> NHWC:
     if Ho <= 0 or Wo <= 0:
         raise RuntimeError("MaxPool2d({}, {}, {}) output of a {}x{} map would be empty".format(k, s, p, x.H, x.W))
     y = torch.empty((x.N, Ho, Wo, x.cpitch), dtype=x.dtype, device=x.device)
-    ctx = _ctx(x.device)
-    _lib.check(_lib.lib().pcv_maxpool2d(ctx, _ptr(x.t), _ptr(y), x.N, x.H, x.W, x.cpitch, k, s, p, 1 if ceil_mode else 0,
-                                        _CODE_OF_TORCH[x.dtype], _stream(x.device)), ctx)
+    _call(x.device, "maxpool2d", _ptr(x.t), _ptr(y), x.N, x.H, x.W, x.cpitch, k, s, p, 1 if ceil_mode else 0, _CODE_OF_TORCH[x.dtype])
     return NHWC(y, x.N, Ho, Wo, x.C, cpitch=x.cpitch)
 
 
@@ -684,10 +676,8 @@ def avgpool2d(x: NHWC, k: int, s: int, out_fp32: bool = False) -> NHWC:
         raise RuntimeError("AvgPool2d kernel {} larger than the {}x{} map".format(k, x.H, x.W))
     Ho, Wo = (x.H - k) // s + 1, (x.W - k) // s + 1
     y = torch.empty((x.N, Ho, Wo, x.cpitch), dtype=torch.float32 if out_fp32 else x.dtype, device=x.device)
-    ctx = _ctx(x.device)
     code = _CODE_OF_TORCH[x.dtype]
-    _lib.check(_lib.lib().pcv_avgpool2d(ctx, _ptr(x.t), _ptr(y), x.N, x.H, x.W, x.cpitch, k, s, code, 0 if out_fp32 else code,
-                                        _stream(x.device)), ctx)
+    _call(x.device, "avgpool2d", _ptr(x.t), _ptr(y), x.N, x.H, x.W, x.cpitch, k, s, code, 0 if out_fp32 else code)
     return NHWC(y, x.N, Ho, Wo, x.C, cpitch=x.cpitch)
 
 
@@ -700,10 +690,9 @@ def avgpool2d_pad(x: NHWC, k: int, s: int, p: int = 0, ceil_mode: bool = False, 
     if Ho <= 0 or Wo <= 0:
         raise RuntimeError("AvgPool2d({}, {}, {}) output of a {}x{} map would be empty".format(k, s, p, x.H, x.W))
     y = torch.empty((x.N, Ho, Wo, x.cpitch), dtype=x.dtype, device=x.device)
-    ctx = _ctx(x.device)
     code = _CODE_OF_TORCH[x.dtype]
-    _lib.check(_lib.lib().pcv_avgpool2d_pad(ctx, _ptr(x.t), _ptr(y), x.N, x.H, x.W, x.cpitch, k, s, p, 1 if ceil_mode else 0,
-                                            1 if count_include_pad else 0, code, code, _stream(x.device)), ctx)
+    _call(x.device, "avgpool2d_pad", _ptr(x.t), _ptr(y), x.N, x.H, x.W, x.cpitch, k, s, p, 1 if ceil_mode else 0,
+          1 if count_include_pad else 0, code, code)
     return NHWC(y, x.N, Ho, Wo, x.C, cpitch=x.cpitch)
 
 
@@ -729,21 +718,17 @@ def mbconv_fused(exp, exp_act: int, dw, dw_act: int, proj, proj_act: int, x: NHW
         return None
     if any(r is not None and r.pad4 is not None for r in (exp, dw, proj)):
         return None
-    for r in (exp, dw, proj):
-        if r is not None and r.bn is not None and r.bn.training:
-            raise RuntimeError("pytorchcv_amd is an inference path: call net.eval() first (BatchNorm is folded)")
-    L, ctx, st = _lib.lib(), _ctx(x.device), _stream(x.device)
+    _require_eval(exp, dw, proj)
     cur = x
     d_exp = None
     if exp is not None:
         d_exp = exp.desc(x, exp_act, 0, False)
         cur = _ShapeOnly(x.N, x.H, x.W, exp.conv.out_channels, x.dtype)
     d_dw = dw.desc(cur, dw_act, 0, False)
-    Ho = (cur.H + d_dw.pad_t + d_dw.pad_b - d_dw.dil_h * (d_dw.kh - 1) - 1) // d_dw.stride_h + 1
-    Wo = (cur.W + d_dw.pad_l + d_dw.pad_r - d_dw.dil_w * (d_dw.kw - 1) - 1) // d_dw.stride_w + 1
+    Ho, Wo = _conv_out(d_dw, cur.H, cur.W)
     mid = _ShapeOnly(x.N, Ho, Wo, dw.conv.out_channels, x.dtype)
     d_proj = proj.desc(mid, proj_act, post_act, residual is not None)
-    if not L.pcv_mbconv_supported(ctypes.byref(d_exp) if d_exp is not None else None, ctypes.byref(d_dw), ctypes.byref(d_proj)):
+    if not _lib.lib().pcv_mbconv_supported(ctypes.byref(d_exp) if d_exp is not None else None, ctypes.byref(d_dw), ctypes.byref(d_proj)):
         return None
     Cout = d_proj.Cout                                           # physical
     if residual is not None and (not residual.dense or residual.dtype != x.dtype or
@@ -755,11 +740,11 @@ def mbconv_fused(exp, exp_act: int, dw, dw_act: int, proj, proj_act: int, x: NHW
     dw.prepare(_PrepHandle(cur, x.device), d_dw)
     proj.prepare(_PrepHandle(mid, x.device), d_proj)
     y = torch.empty((x.N, Ho, Wo, Cout), dtype=x.dtype, device=x.device)
-    _lib.check(L.pcv_mbconv_fused(ctx, ctypes.byref(d_exp) if d_exp is not None else None, ctypes.byref(d_dw), ctypes.byref(d_proj),
-                                  _ptr(x.t), _ptr(exp.packed) if exp is not None else None,
-                                  _ptr(exp.scale) if exp is not None else None, _ptr(exp.shift) if exp is not None else None,
-                                  _ptr(dw.packed), _ptr(dw.scale), _ptr(dw.shift), _ptr(proj.packed), _ptr(proj.scale),
-                                  _ptr(proj.shift), _ptr(residual.t) if residual is not None else None, _ptr(y), st), ctx)
+    _call(x.device, "mbconv_fused", ctypes.byref(d_exp) if d_exp is not None else None, ctypes.byref(d_dw), ctypes.byref(d_proj),
+          _ptr(x.t), _ptr(exp.packed) if exp is not None else None,
+          _ptr(exp.scale) if exp is not None else None, _ptr(exp.shift) if exp is not None else None,
+          _ptr(dw.packed), _ptr(dw.scale), _ptr(dw.shift), _ptr(proj.packed), _ptr(proj.scale),
+          _ptr(proj.shift), _ptr(residual.t) if residual is not None else None, _ptr(y))
     return NHWC(y, x.N, Ho, Wo, proj.conv.out_channels, cpitch=Cout)
 
 
@@ -802,15 +787,13 @@ class BnActRunner(object):
         def padded(t, fill):
             t = t.detach().float()
             return (F.pad(t, (0, C - Cl), value=fill) if C != Cl else t).contiguous()
-        L, ctx, st = _lib.lib(), _ctx(dev), _stream(dev)
         g = padded(bn.weight if bn.weight is not None else torch.ones(Cl, device=dev), 0.0)
         b = padded(bn.bias if bn.bias is not None else torch.zeros(Cl, device=dev), 0.0)
         m = padded(bn.running_mean, 0.0)
         v = padded(bn.running_var, 1.0)
         scale = torch.empty(C, dtype=torch.float32, device=dev)
         shift = torch.empty(C, dtype=torch.float32, device=dev)
-        _lib.check(L.pcv_bn_fold(ctx, C, _ptr(g), _ptr(b), _ptr(m), _ptr(v), ctypes.c_float(bn.eps), None, _ptr(scale),
-                                 _ptr(shift), st), ctx)
+        _call(dev, "bn_fold", C, _ptr(g), _ptr(b), _ptr(m), _ptr(v), ctypes.c_float(bn.eps), None, _ptr(scale), _ptr(shift))
         torch.cuda.current_stream(dev).synchronize()
         self.scale, self.shift, self._key = scale, shift, key
 
@@ -822,8 +805,7 @@ class BnActRunner(object):
         self._key = None
 
     def run(self, x: NHWC, act: int) -> NHWC:
-        if self.bn.training:
-            raise RuntimeError("pytorchcv_amd is an inference path: call net.eval() first (BatchNorm is folded)")
+        _require_eval(self)
         if x.wpitch != x.W:
             raise RuntimeError("BatchNorm + activation on a row-padded handle")
         if x.C != self.bn.num_features:
@@ -831,9 +813,8 @@ class BnActRunner(object):
         self.prepare(x)
         CP = round8(x.C)                        # physical channels processed (x may also be the prefix of a wider concat buffer)
         y = torch.empty((x.N, x.H, x.W, CP), dtype=x.dtype, device=x.device)
-        ctx = _ctx(x.device)
-        _lib.check(_lib.lib().pcv_bn_act(ctx, _ptr(x.t), _ptr(self.scale), _ptr(self.shift), _ptr(y), x.N * x.H * x.W, CP,
-                                         x.cpitch, act, _CODE_OF_TORCH[x.dtype], _stream(x.device)), ctx)
+        _call(x.device, "bn_act", _ptr(x.t), _ptr(self.scale), _ptr(self.shift), _ptr(y), x.N * x.H * x.W, CP, x.cpitch, act,
+              _CODE_OF_TORCH[x.dtype])
         return NHWC(y, x.N, x.H, x.W, x.C, cpitch=CP)
 
 
@@ -842,37 +823,44 @@ def global_avgpool(x: NHWC, out_fp32: bool = False) -> NHWC:
     if not x.dense:
         raise RuntimeError("avg-pool on a padded handle")
     y = torch.empty((x.N, 1, 1, x.cpitch), dtype=torch.float32 if out_fp32 else x.dtype, device=x.device)
-    ctx = _ctx(x.device)
     code = _CODE_OF_TORCH[x.dtype]
-    _lib.check(_lib.lib().pcv_global_avgpool(ctx, _ptr(x.t), _ptr(y), x.N, x.H * x.W, x.cpitch, code, 0 if out_fp32 else code,
-                                             _stream(x.device)), ctx)
+    _call(x.device, "global_avgpool", _ptr(x.t), _ptr(y), x.N, x.H * x.W, x.cpitch, code, 0 if out_fp32 else code)
     return NHWC(y, x.N, 1, 1, x.C, cpitch=x.cpitch)
+
+
+def se_excite(v: torch.Tensor, w1, b1, w2, b2, mid_act: int, out_act: int) -> torch.Tensor:
+    """The two fp32 layers of an excitation on a contiguous fp32 [N, C] tensor (pcv_se_excite): out_act(w2 . mid_act(w1 . v + b1) + b2)
+    with w1 [M, C], b1 [M], w2 [C, M], b2 [C] -> fp32 [N, C]."""
+    N, C, M = v.shape[0], v.shape[1], w1.shape[0]
+    mid = torch.empty((N, M), dtype=torch.float32, device=v.device)
+    gate = torch.empty((N, C), dtype=torch.float32, device=v.device)
+    _call(v.device, "se_excite", _ptr(v), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(mid), _ptr(gate), N, C, M, mid_act, out_act)
+    return gate
+
+
+def se_scale(x: NHWC, gate: torch.Tensor, residual: NHWC | None = None, post_act: int = 0) -> NHWC:
+    """post_act(x * gate + residual) with a per-image, per-channel fp32 gate [N, x.cpitch] (pcv_se_scale). The callers have checked that
+    `x` is dense and that `gate` is a contiguous fp32 tensor of that shape on x's device; only the residual is checked here."""
+    if residual is not None and (residual.t.shape != x.t.shape or residual.dtype != x.dtype):
+        raise RuntimeError("SE residual shape/dtype mismatch")
+    y = torch.empty_like(x.t)
+    _call(x.device, "se_scale", _ptr(x.t), _ptr(gate), _ptr(residual.t) if residual is not None else None, _ptr(y), x.N, x.H * x.W,
+          x.cpitch, post_act, _CODE_OF_TORCH[x.dtype])
+    return NHWC(y, x.N, x.H, x.W, x.C, cpitch=x.cpitch)
 
 
 def se_forward(x: NHWC, w1, b1, w2, b2, mid_act: int, out_act: int, residual: NHWC | None, post_act: int) -> NHWC:
     """SEBlock on the hot path: squeeze -> excite (fp32) -> scale (+ residual, + activation)."""
     if not x.dense:
         raise RuntimeError("SE on a padded handle")
-    L, ctx, st = _lib.lib(), _ctx(x.device), _stream(x.device)
-    code = _CODE_OF_TORCH[x.dtype]
     CP = x.cpitch                                              # physical channels; the FC weights get zero columns / rows for the pads
     if CP != x.C:
         w1 = F.pad(w1, (0, CP - x.C)).contiguous()
         w2 = F.pad(w2, (0, 0, 0, CP - x.C)).contiguous()
         b2 = F.pad(b2, (0, CP - x.C)).contiguous()
     mean = torch.empty((x.N, CP), dtype=torch.float32, device=x.device)
-    gate = torch.empty((x.N, CP), dtype=torch.float32, device=x.device)
-    _lib.check(L.pcv_se_squeeze(ctx, _ptr(x.t), _ptr(mean), x.N, x.H * x.W, CP, code, st), ctx)
-    M = w1.shape[0]
-    mid = torch.empty((x.N, M), dtype=torch.float32, device=x.device)
-    _lib.check(L.pcv_se_excite(ctx, _ptr(mean), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(mid), _ptr(gate), x.N, CP, M,
-                               mid_act, out_act, st), ctx)
-    y = torch.empty_like(x.t)
-    if residual is not None and (residual.t.shape != x.t.shape or residual.dtype != x.dtype):
-        raise RuntimeError("SE residual shape/dtype mismatch")
-    _lib.check(L.pcv_se_scale(ctx, _ptr(x.t), _ptr(gate), _ptr(residual.t) if residual is not None else None, _ptr(y),
-                              x.N, x.H * x.W, CP, post_act, code, st), ctx)
-    return NHWC(y, x.N, x.H, x.W, x.C, cpitch=CP)
+    _call(x.device, "se_squeeze", _ptr(x.t), _ptr(mean), x.N, x.H * x.W, CP, _CODE_OF_TORCH[x.dtype])
+    return se_scale(x, se_excite(mean, w1, b1, w2, b2, mid_act, out_act), residual, post_act)
 
 
 def splat_forward(x: NHWC, radix: int, groups: int, w1, b1, w2, b2, residual: NHWC | None = None, post_act: int = 0) -> NHWC:
@@ -885,50 +873,71 @@ def splat_forward(x: NHWC, radix: int, groups: int, w1, b1, w2, b2, residual: NH
     C = x.C // radix
     if C % 8:
         raise NotImplementedError("split attention with {} channels per split: the MI355X path needs multiples of 8".format(C))
-    L, ctx, st = _lib.lib(), _ctx(x.device), _stream(x.device)
     code = _CODE_OF_TORCH[x.dtype]
     N, HW, M = x.N, x.H * x.W, int(w1.shape[0])
     s = torch.empty((N, C), dtype=torch.float32, device=x.device)
-    _lib.check(L.pcv_splat_squeeze(ctx, _ptr(x.t), _ptr(s), N, HW, C, radix, code, st), ctx)
+    _call(x.device, "splat_squeeze", _ptr(x.t), _ptr(s), N, HW, C, radix, code)
     mid = torch.empty((N, M), dtype=torch.float32, device=x.device)
     logits = torch.empty((N, radix * C), dtype=torch.float32, device=x.device)
     att = torch.empty((N, radix * C), dtype=torch.float32, device=x.device)
-    _lib.check(L.pcv_splat_excite(ctx, _ptr(s), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(mid), _ptr(logits), _ptr(att), N, C, M,
-                                  radix, groups, st), ctx)
+    _call(x.device, "splat_excite", _ptr(s), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(mid), _ptr(logits), _ptr(att), N, C, M,
+          radix, groups)
     y = torch.empty((N, x.H, x.W, C), dtype=x.dtype, device=x.device)
     if residual is not None and (tuple(residual.t.shape) != tuple(y.shape) or residual.dtype != x.dtype):
         raise RuntimeError("split-attention residual shape/dtype mismatch: {} vs {}".format(tuple(residual.t.shape), tuple(y.shape)))
-    _lib.check(L.pcv_splat_combine(ctx, _ptr(x.t), _ptr(att), _ptr(residual.t) if residual is not None else None, _ptr(y), N, HW,
-                                   C, radix, post_act, code, st), ctx)
+    _call(x.device, "splat_combine", _ptr(x.t), _ptr(att), _ptr(residual.t) if residual is not None else None, _ptr(y), N, HW, C, radix,
+          post_act, code)
+    return NHWC(y, N, x.H, x.W, C)
+
+
+def _cbam_handle(x: NHWC):
+    """The CBAM launches take a dense handle with a multiple of 8 channels; anything else is refused before any of them."""
+    if not x.dense or x.C % 8:
+        raise NotImplementedError("CBAM on {} channels: the MI355X path needs a dense handle with a multiple of 8".format(x.C))
+
+
+def cbam_channel_gate(x: NHWC, w1, b1, w2, b2) -> torch.Tensor:
+    """CBAM's channel gate (ChannelGate, reference cbamresnet.py:48-80) as an fp32 [N, C] factor: mean and max over the map
+    (pcv_cbam_pool) -> shared fp32 MLP (w1 [M, C], b1 [M], w2 [C, M], b2 [C]) on both, summed, sigmoid (pcv_cbam_excite)."""
+    _cbam_handle(x)
+    N, C, M = x.N, x.C, int(w1.shape[0])
+    if tuple(w1.shape) != (M, C) or tuple(w2.shape) != (C, M):
+        raise RuntimeError("CBAM weights do not fit {} channels".format(C))
+    f32 = dict(dtype=torch.float32, device=x.device)
+    s = torch.empty((N, 2, C), **f32)
+    _call(x.device, "cbam_pool", _ptr(x.t), _ptr(s), N, x.H * x.W, C, _CODE_OF_TORCH[x.dtype])
+    mid = torch.empty((N, 2, M), **f32)
+    gate = torch.empty((N, C), **f32)
+    _call(x.device, "cbam_excite", _ptr(s), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(mid), _ptr(gate), N, C, M)
+    return gate
+
+
+def cbam_spatial(x: NHWC, gate: torch.Tensor | None, w7, scale, shift, residual: NHWC | None = None, post_act: int = 0) -> NHWC:
+    """CBAM's spatial stage on x * gate (SpatialGate, reference cbamresnet.py:83-102; gate fp32 [N, C], None = ones: the stand-alone
+    module): per-pixel max and mean over the channels (pcv_cbam_spatial_pool) -> 7x7 convolution 2 -> 1 (w7 fp32 [2, 7, 7]; `scale` /
+    `shift`: one device float each, its folded BatchNorm), sigmoid -> y = post_act((x * gate) * spatial gate + residual)
+    (pcv_cbam_apply). x * gate is never stored."""
+    _cbam_handle(x)
+    if w7.numel() != 98 or scale.numel() != 1 or shift.numel() != 1:
+        raise RuntimeError("CBAM weights do not fit {} channels".format(x.C))
+    code = _CODE_OF_TORCH[x.dtype]
+    N, HW, C = x.N, x.H * x.W, x.C
+    if gate is None:
+        gate = torch.ones((N, C), dtype=torch.float32, device=x.device)
+    p = torch.empty((N, HW, 2), dtype=torch.float32, device=x.device)
+    _call(x.device, "cbam_spatial_pool", _ptr(x.t), _ptr(gate), _ptr(p), N, HW, C, code)
+    y = torch.empty_like(x.t)
+    if residual is not None and (tuple(residual.t.shape) != tuple(x.t.shape) or residual.dtype != x.dtype):
+        raise RuntimeError("CBAM residual shape/dtype mismatch: {} vs {}".format(tuple(residual.t.shape), tuple(x.t.shape)))
+    _call(x.device, "cbam_apply", _ptr(x.t), _ptr(gate), _ptr(p), _ptr(w7), _ptr(scale), _ptr(shift),
+          _ptr(residual.t) if residual is not None else None, _ptr(y), N, x.H, x.W, C, post_act, code)
     return NHWC(y, N, x.H, x.W, C)
 
 
 def cbam_forward(x: NHWC, w1, b1, w2, b2, w7, scale, shift, residual: NHWC | None = None, post_act: int = 0) -> NHWC:
-    """CBAM block on the hot path (CbamBlock, reference cbamresnet.py:105-128): mean and max over the map -> shared fp32 MLP (w1 [M, C],
-    b1 [M], w2 [C, M], b2 [C]) on both, summed, sigmoid -> per-pixel max and mean over the channels of x * gate -> 7x7 convolution
-    2 -> 1 (w7 fp32 [2, 7, 7]; `scale` / `shift`: one device float each, its folded BatchNorm), sigmoid -> y = post_act((x * gate) *
-    spatial gate + residual). Four launches; the only tensor of x's size they write is y."""
-    if not x.dense or x.C % 8:
-        raise NotImplementedError("CBAM on {} channels: the MI355X path needs a dense handle with a multiple of 8".format(x.C))
-    L, ctx, st = _lib.lib(), _ctx(x.device), _stream(x.device)
-    code = _CODE_OF_TORCH[x.dtype]
-    N, HW, C, M = x.N, x.H * x.W, x.C, int(w1.shape[0])
-    if tuple(w1.shape) != (M, C) or tuple(w2.shape) != (C, M) or w7.numel() != 98 or scale.numel() != 1 or shift.numel() != 1:
-        raise RuntimeError("CBAM weights do not fit {} channels".format(C))
-    f32 = dict(dtype=torch.float32, device=x.device)
-    s = torch.empty((N, 2, C), **f32)
-    _lib.check(L.pcv_cbam_pool(ctx, _ptr(x.t), _ptr(s), N, HW, C, code, st), ctx)
-    mid = torch.empty((N, 2, M), **f32)
-    gate = torch.empty((N, C), **f32)
-    _lib.check(L.pcv_cbam_excite(ctx, _ptr(s), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(mid), _ptr(gate), N, C, M, st), ctx)
-    p = torch.empty((N, HW, 2), **f32)
-    _lib.check(L.pcv_cbam_spatial_pool(ctx, _ptr(x.t), _ptr(gate), _ptr(p), N, HW, C, code, st), ctx)
-    y = torch.empty_like(x.t)
-    if residual is not None and (tuple(residual.t.shape) != tuple(x.t.shape) or residual.dtype != x.dtype):
-        raise RuntimeError("CBAM residual shape/dtype mismatch: {} vs {}".format(tuple(residual.t.shape), tuple(x.t.shape)))
-    _lib.check(L.pcv_cbam_apply(ctx, _ptr(x.t), _ptr(gate), _ptr(p), _ptr(w7), _ptr(scale), _ptr(shift),
-                                _ptr(residual.t) if residual is not None else None, _ptr(y), N, x.H, x.W, C, post_act, code, st), ctx)
-    return NHWC(y, N, x.H, x.W, C)
+    """CBAM block on the hot path (CbamBlock, reference cbamresnet.py:105-128): `cbam_channel_gate`, then `cbam_spatial` with that
+    gate. Four launches; the only tensor of x's size they write is y."""
+    return cbam_spatial(x, cbam_channel_gate(x, w1, b1, w2, b2), w7, scale, shift, residual, post_act)
 
 
 def classify(logits: torch.Tensor, k: int = 0, labels=None, probs: bool = False, nll: bool = False) -> dict:
@@ -941,7 +950,6 @@ def classify(logits: torch.Tensor, k: int = 0, labels=None, probs: bool = False,
     if not torch.is_tensor(logits) or logits.dim() != 2 or logits.dtype != torch.float32:
         raise TypeError("expected fp32 logits [N, J]")
     dev = logits.device
-    ctx = _ctx(dev)
     logits = logits.contiguous()
     N, J = int(logits.shape[0]), int(logits.shape[1])
     k = int(k)
@@ -960,7 +968,6 @@ def classify(logits: torch.Tensor, k: int = 0, labels=None, probs: bool = False,
         out["rank"] = torch.empty((N,), dtype=torch.int32, device=dev)
     if nll:
         out["nll"] = torch.empty((N,), dtype=torch.float32, device=dev)
-    _lib.check(_lib.lib().pcv_classify_f32(ctx, _ptr(logits), N, J, k, _ptr(out.get("ids")), _ptr(out.get("values")),
-                                           _ptr(out.get("probs")), _ptr(labels), _ptr(out.get("rank")), _ptr(out.get("nll")),
-                                           _stream(dev)), ctx)
+    _call(dev, "classify_f32", _ptr(logits), N, J, k, _ptr(out.get("ids")), _ptr(out.get("values")), _ptr(out.get("probs")), _ptr(labels),
+          _ptr(out.get("rank")), _ptr(out.get("nll")))
     return out

@@ -99,9 +99,8 @@ def preprocess_u8(frames: torch.Tensor, img_size: int = 224, dtype: str = "bf16"
     h = _input_handle(out, n, img_size, c, dtype, dev)
     y, wp = h.t, h.wpitch
     m, s = _norm_consts(mean, std, c, dev)
-    ctx = engine._ctx(dev)
-    _lib.check(_lib.lib().pcv_preprocess_u8(ctx, engine._ptr(frames), engine._ptr(y), n, hs, ws, c, top, left, img_size, img_size,
-                                            wp, engine._ptr(m), engine._ptr(s), code, engine._stream(dev)), ctx)
+    engine._call(dev, "preprocess_u8", engine._ptr(frames), engine._ptr(y), n, hs, ws, c, top, left, img_size, img_size, wp,
+                 engine._ptr(m), engine._ptr(s), code)
     return h
 
 
@@ -153,9 +152,8 @@ def preprocess_frames(frames, img_size: int = 224, img_scale: float = 0.875, dty
     h = _input_handle(out, n, img_size, c, dtype, dev)
     y, wp = h.t, h.wpitch
     m, s = _norm_consts(mean, std, c, dev)
-    ctx = engine._ctx(dev)
-    _lib.check(L.pcv_resize_crop_u8(ctx, plan.data_ptr(), engine._ptr(plan_dev), nbytes.value, engine._ptr(y), wp, engine._ptr(m),
-                                    engine._ptr(s), code, engine._stream(dev)), ctx)
+    engine._call(dev, "resize_crop_u8", plan.data_ptr(), engine._ptr(plan_dev), nbytes.value, engine._ptr(y), wp, engine._ptr(m),
+                 engine._ptr(s), code)
     return h
 
 

@@ -15,7 +15,7 @@ from .common.conv import conv1x1_block, conv7x7_block
 from .common.att import fold_bn_into_fc, _FoldedMlp
 from .resnet import ResInitBlock, ResBlock, ResBottleneck
 from ._tail import AvgPool2dNHWC, LinearHead, run_net, maybe_load_pretrained, init_conv_params, DEFAULT_ROOT
-from .. import engine, _lib
+from .. import engine
 
 
 class MLP(nn.Module):
@@ -35,15 +35,9 @@ class MLP(nn.Module):
     def forward(self, x):
         x = x.reshape(x.size(0), -1).float().contiguous()
         w1, b1, w2, b2 = self.weights()
-        N, C, M = x.shape[0], w1.shape[1], w1.shape[0]
-        if x.shape[1] != C:
-            raise RuntimeError("MLP expects {} features, got {}".format(C, x.shape[1]))
-        mid = torch.empty((N, M), dtype=torch.float32, device=x.device)
-        y = torch.empty((N, C), dtype=torch.float32, device=x.device)
-        ctx, p = engine._ctx(x.device), engine._ptr
-        _lib.check(_lib.lib().pcv_se_excite(ctx, p(x), p(w1), p(b1), p(w2), p(b2), p(mid), p(y), N, C, M, engine.act_code(self.activ), 0,
-                                            engine._stream(x.device)), ctx)
-        return y
+        if x.shape[1] != w1.shape[1]:
+            raise RuntimeError("MLP expects {} features, got {}".format(w1.shape[1], x.shape[1]))
+        return engine.se_excite(x, w1, b1, w2, b2, engine.act_code(self.activ), 0)
 
 
 class ChannelGate(nn.Module):
@@ -58,19 +52,7 @@ class ChannelGate(nn.Module):
         self.sigmoid = nn.Sigmoid()
 
     def _run(self, a):
-        if not a.dense or a.C % 8:
-            raise NotImplementedError("CBAM on {} channels: the MI355X path needs a dense handle with a multiple of 8".format(a.C))
-        w1, b1, w2, b2 = self.mlp.weights()
-        L, ctx, st, p = _lib.lib(), engine._ctx(a.device), engine._stream(a.device), engine._ptr
-        code = engine._CODE_OF_TORCH[a.dtype]
-        N, HW, C, M = a.N, a.H * a.W, a.C, w1.shape[0]
-        f32 = dict(dtype=torch.float32, device=a.device)
-        s, mid, gate = torch.empty((N, 2, C), **f32), torch.empty((N, 2, M), **f32), torch.empty((N, C), **f32)
-        _lib.check(L.pcv_cbam_pool(ctx, p(a.t), p(s), N, HW, C, code, st), ctx)
-        _lib.check(L.pcv_cbam_excite(ctx, p(s), p(w1), p(b1), p(w2), p(b2), p(mid), p(gate), N, C, M, st), ctx)
-        y = torch.empty_like(a.t)
-        _lib.check(L.pcv_se_scale(ctx, p(a.t), p(gate), None, p(y), N, HW, C, 0, code, st), ctx)
-        return engine.NHWC(y, N, a.H, a.W, C)
+        return engine.se_scale(a, engine.cbam_channel_gate(a, *self.mlp.weights()))
 
     def forward(self, x):
         return engine.boundary(self, x, self._run)
@@ -100,18 +82,7 @@ class SpatialGate(nn.Module):
         return self._pcv_stencil.get(srcs, build)
 
     def _run(self, a):
-        if not a.dense or a.C % 8:
-            raise NotImplementedError("CBAM on {} channels: the MI355X path needs a dense handle with a multiple of 8".format(a.C))
-        w7, scale, shift = self.stencil()
-        L, ctx, st, p = _lib.lib(), engine._ctx(a.device), engine._stream(a.device), engine._ptr
-        code = engine._CODE_OF_TORCH[a.dtype]
-        N, HW, C = a.N, a.H * a.W, a.C
-        ones = torch.ones((N, C), dtype=torch.float32, device=a.device)
-        pm = torch.empty((N, HW, 2), dtype=torch.float32, device=a.device)
-        _lib.check(L.pcv_cbam_spatial_pool(ctx, p(a.t), p(ones), p(pm), N, HW, C, code, st), ctx)
-        y = torch.empty_like(a.t)
-        _lib.check(L.pcv_cbam_apply(ctx, p(a.t), p(ones), p(pm), p(w7), p(scale), p(shift), None, p(y), N, a.H, a.W, C, 0, code, st), ctx)
-        return engine.NHWC(y, N, a.H, a.W, C)
+        return engine.cbam_spatial(a, None, *self.stencil())
 
     def forward(self, x):
         return engine.boundary(self, x, self._run)

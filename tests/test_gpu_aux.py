@@ -842,3 +842,108 @@ def test_refusals(dtype, cuda_device):
     torch.cuda.synchronize()
     for fl in (flat, flat32):                                                           # a refused call wrote nothing
         assert bool((bits(fl).cpu() == SENTINEL[fl.dtype]).all())
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_refusals_squeeze_excite_pool_fold_preprocess(dtype, cuda_device):
+    """the same for the entry points test_refusals does not reach: pcv_se_squeeze / _excite / _scale, pcv_fc_f32, pcv_avgpool2d,
+    pcv_global_avgpool's types, pcv_bn_fold and pcv_preprocess_u8"""
+    lb, L, ctx = _lib()
+    st = _stream()
+    code = CODE[dtype]
+    other = 2 if code == 1 else 1                      # a 16-bit type that is neither the input's nor fp32
+    x = torch.zeros(1 << 14, dtype=TDT[dtype], device=cuda_device)
+    f = torch.zeros(1 << 14, dtype=torch.float32, device=cuda_device)
+    u8 = torch.zeros(1 << 14, dtype=torch.uint8, device=cuda_device)
+    flat, y = guarded((1 << 14,), TDT[dtype], cuda_device)
+    flat32, y32 = guarded((1 << 14,), torch.float32, cuda_device)
+    flat32b, z32 = guarded((1 << 14,), torch.float32, cuda_device)
+    X, Y, Fp, Y32, Z32, U8 = _p(x), _p(y), _p(f), _p(y32), _p(z32), _p(u8)
+
+    def invalid(name, rc):
+        with pytest.raises(lb.PcvError) as e:
+            lb.check(rc, ctx)
+        assert e.value.code == -1 and name in str(e.value), (name, str(e.value))
+
+    n = "pcv_se_squeeze"
+    invalid(n, L.pcv_se_squeeze(ctx, None, Y32, 2, 49, 16, code, st))
+    invalid(n, L.pcv_se_squeeze(ctx, X, None, 2, 49, 16, code, st))
+    invalid(n, L.pcv_se_squeeze(ctx, X, Y32, 2, 49, 12, code, st))                    # C % 8
+    invalid(n, L.pcv_se_squeeze(ctx, X, Y32, 2, 49, 16, 3, st))                       # no such dtype
+    n = "pcv_se_excite"
+    good = [Fp, Fp, Fp, Fp, Fp, Z32, Y32]                                             # mean, w1, b1, w2, b2, mid, gate
+    for i in range(7):
+        invalid(n, L.pcv_se_excite(ctx, *(good[:i] + [None] + good[i + 1:]), 2, 16, 4, 1, 3, st))
+    invalid(n, L.pcv_se_excite(ctx, *good, 2, 16, 0, 1, 3, st))                       # M = 0
+    n = "pcv_se_scale"
+    invalid(n, L.pcv_se_scale(ctx, None, Fp, None, Y, 2, 49, 16, 0, code, st))
+    invalid(n, L.pcv_se_scale(ctx, X, None, None, Y, 2, 49, 16, 0, code, st))
+    invalid(n, L.pcv_se_scale(ctx, X, Fp, None, None, 2, 49, 16, 0, code, st))
+    invalid(n, L.pcv_se_scale(ctx, X, Fp, None, Y, 2, 49, 12, 0, code, st))           # C % 8
+    invalid(n, L.pcv_se_scale(ctx, X, Fp, None, Y, 2, 49, 16, 0, 3, st))              # no such dtype
+    n = "pcv_fc_f32"
+    good = [Fp, Fp, Fp, Y32]                                                          # in, w, b, out
+    for i in range(4):
+        invalid(n, L.pcv_fc_f32(ctx, *(good[:i] + [None] + good[i + 1:]), 2, 16, 4, 1, st))
+    invalid(n, L.pcv_fc_f32(ctx, *good, 2, 0, 4, 1, st))                              # K = 0
+    n = "pcv_avgpool2d"
+    for Yo, oc in ((Y, code), (Y32, 0)):
+        invalid(n, L.pcv_avgpool2d(ctx, None, Yo, 2, 8, 8, 16, 3, 2, code, oc, st))
+        invalid(n, L.pcv_avgpool2d(ctx, X, None, 2, 8, 8, 16, 3, 2, code, oc, st))
+        invalid(n, L.pcv_avgpool2d(ctx, X, Yo, 2, 8, 8, 12, 3, 2, code, oc, st))      # C % 8
+        invalid(n, L.pcv_avgpool2d(ctx, X, Yo, 2, 2, 8, 16, 3, 1, code, oc, st))      # k > H
+        invalid(n, L.pcv_avgpool2d(ctx, X, Yo, 2, 8, 2, 16, 3, 1, code, oc, st))      # k > W
+    invalid(n, L.pcv_avgpool2d(ctx, X, Y, 2, 8, 8, 16, 3, 2, 3, 3, st))               # no such dtype
+    invalid(n, L.pcv_avgpool2d(ctx, X, Y, 2, 8, 8, 16, 3, 2, code, other, st))        # neither the input's type nor fp32
+    invalid(n, L.pcv_avgpool2d(ctx, X, Y, 2, 8, 8, 16, 8, 1, code, other, st))        # ... on the whole-map form as well
+    n = "pcv_global_avgpool"
+    invalid(n, L.pcv_global_avgpool(ctx, X, Y, 2, 49, 16, 3, 3, st))                  # no such dtype
+    invalid(n, L.pcv_global_avgpool(ctx, X, Y, 2, 49, 16, code, 3, st))               # no such out_dtype
+    invalid(n, L.pcv_global_avgpool(ctx, X, Y32, 2, 49, 12, code, 0, st))             # C % 8, fp32 out
+    invalid(n, L.pcv_global_avgpool(ctx, None, Y32, 2, 49, 16, code, 0, st))
+    invalid(n, L.pcv_global_avgpool(ctx, X, None, 2, 49, 16, code, 0, st))
+    n = "pcv_bn_fold"
+    invalid(n, L.pcv_bn_fold(ctx, 0, Fp, Fp, Fp, Fp, 1e-5, None, Y32, Z32, st))       # C <= 0
+    invalid(n, L.pcv_bn_fold(ctx, -8, Fp, Fp, Fp, Fp, 1e-5, None, Y32, Z32, st))
+    invalid(n, L.pcv_bn_fold(ctx, 16, Fp, Fp, Fp, Fp, 1e-5, None, None, Z32, st))
+    invalid(n, L.pcv_bn_fold(ctx, 16, Fp, Fp, Fp, Fp, 1e-5, None, Y32, None, st))
+    stats = [Fp, Fp, Fp, Fp]
+    for i in range(4):                                                                # three of gamma / beta / mean / var
+        invalid(n, L.pcv_bn_fold(ctx, 16, *(stats[:i] + [None] + stats[i + 1:]), 1e-5, Fp, Y32, Z32, st))
+    n = "pcv_preprocess_u8"
+    # (x, y, N, Hs, Ws, C, top, left, H, W, wpitch, mean, inv_std, dtype)
+    invalid(n, L.pcv_preprocess_u8(ctx, None, Y, 2, 12, 14, 3, 1, 2, 8, 8, 8, Fp, Fp, code, st))
+    invalid(n, L.pcv_preprocess_u8(ctx, U8, None, 2, 12, 14, 3, 1, 2, 8, 8, 8, Fp, Fp, code, st))
+    invalid(n, L.pcv_preprocess_u8(ctx, U8, Y, 2, 12, 14, 3, 1, 2, 8, 8, 8, None, Fp, code, st))
+    invalid(n, L.pcv_preprocess_u8(ctx, U8, Y, 2, 12, 14, 3, 1, 2, 8, 8, 8, Fp, None, code, st))
+    invalid(n, L.pcv_preprocess_u8(ctx, U8, Y, 2, 12, 14, 3, 5, 2, 8, 8, 8, Fp, Fp, code, st))     # top + H > Hs
+    invalid(n, L.pcv_preprocess_u8(ctx, U8, Y, 2, 12, 14, 3, 1, 7, 8, 8, 8, Fp, Fp, code, st))     # left + W > Ws
+    invalid(n, L.pcv_preprocess_u8(ctx, U8, Y, 2, 12, 14, 3, -1, 2, 8, 8, 8, Fp, Fp, code, st))    # top < 0
+    invalid(n, L.pcv_preprocess_u8(ctx, U8, Y, 2, 12, 14, 5, 1, 2, 8, 8, 8, Fp, Fp, code, st))     # C > 4
+    invalid(n, L.pcv_preprocess_u8(ctx, U8, Y, 2, 12, 14, 3, 1, 2, 8, 8, 6, Fp, Fp, code, st))     # wpitch < W
+    invalid(n, L.pcv_preprocess_u8(ctx, U8, Y, 2, 12, 14, 3, 1, 2, 8, 8, 8, Fp, Fp, 3, st))        # no such dtype
+    torch.cuda.synchronize()
+    for fl in (flat, flat32, flat32b):                                                # a refused call wrote nothing
+        assert bool((bits(fl).cpu() == SENTINEL[fl.dtype]).all())
+
+
+def test_flat_grid_refusals(cuda_device):
+    """a flat launch whose block count does not fit a 32-bit grid is refused with PCV_ERR_TOO_LARGE before anything is launched (such a
+    call used to launch the count's low 32 bits: 2^32 blocks became a grid of 0). The pointers are never dereferenced."""
+    lb, L, ctx = _lib()
+    st = _stream()
+    x = torch.zeros(1 << 10, dtype=torch.bfloat16, device=cuda_device)
+    f = torch.zeros(1 << 10, dtype=torch.float32, device=cuda_device)
+    flat, y = guarded((1 << 10,), torch.bfloat16, cuda_device)
+    X, Y, Fp = _p(x), _p(y), _p(f)
+
+    def too_large(name, rc):
+        with pytest.raises(lb.PcvError) as e:
+            lb.check(rc, ctx)
+        assert e.value.code == lb.PCV_ERR_TOO_LARGE == -4 and name in str(e.value), (name, str(e.value))
+
+    too_large("pcv_bn_act", L.pcv_bn_act(ctx, X, Fp, Fp, Y, 1 << 40, 8, 8, 1, 1, st))                   # 2^40 chunks: 2^32 blocks
+    too_large("pcv_channel_slice", L.pcv_channel_slice(ctx, X, Y, 1 << 40, 8, 0, 8, 8, 1, st))
+    too_large("pcv_maxpool2d", L.pcv_maxpool2d(ctx, X, Y, 2 ** 31 - 1, 4096, 4096, 8, 1, 1, 0, 0, 1, st))
+    torch.cuda.synchronize()
+    assert bool((bits(flat).cpu() == SENTINEL[flat.dtype]).all())

@@ -195,6 +195,41 @@ def test_product_never_imports_the_oracle():
                 assert not re.search(r"^\s*(from|import)\s+oracle\b", text, flags=re.M), "{} imports oracle".format(f)
 
 
+def test_models_reach_the_library_through_engine_only():
+    """No file under pytorchcv_amd/models/ imports the ctypes binding or touches a private name of engine - under whatever name the
+    file imports engine, by attribute or through getattr with a literal name: every launch of a model goes through one of engine's
+    public functions."""
+    import ast
+    seen = 0
+    for base, _, files in os.walk(os.path.join(ROOT, "pytorchcv_amd", "models")):
+        for f in sorted(files):
+            if not f.endswith(".py"):
+                continue
+            path = os.path.join(base, f)
+            tree = ast.parse(open(path).read(), filename=path)
+            owners = {"engine"}                                   # the names engine goes by in this file
+            for node in ast.walk(tree):
+                if isinstance(node, (ast.Import, ast.ImportFrom)):
+                    module = node.module or "" if isinstance(node, ast.ImportFrom) else ""
+                    for a in node.names:
+                        assert "_lib" not in (module.split(".")[-1], a.name.split(".")[-1]), "{} imports _lib".format(path)
+                        if a.name.split(".")[-1] == "engine":
+                            owners.add(a.asname or a.name.split(".")[-1])
+                        assert not (module.split(".")[-1] == "engine" and a.name.startswith("_")), \
+                            "{} imports engine.{}".format(path, a.name)
+            for node in ast.walk(tree):
+                if isinstance(node, ast.Attribute) and node.attr.startswith("_") and not node.attr.startswith("__"):
+                    owner = node.value.id if isinstance(node.value, ast.Name) else getattr(node.value, "attr", None)
+                    assert owner not in owners, "{} uses engine.{}".format(path, node.attr)
+                if isinstance(node, ast.Call) and isinstance(node.func, ast.Name) and node.func.id == "getattr" and len(node.args) >= 2:
+                    obj, name = node.args[0], node.args[1]
+                    owner = obj.id if isinstance(obj, ast.Name) else getattr(obj, "attr", None)
+                    private = isinstance(name, ast.Constant) and isinstance(name.value, str) and name.value.startswith("_")
+                    assert not (owner in owners and private), "{} reaches engine.{} through getattr".format(path, name.value)
+            seen += 1
+    assert seen >= 20                                  # the walk found the model files
+
+
 # ---- reference interface mirror -------------------------------------------------------------------------------
 def test_get_model_contract():
     from pytorchcv_amd.model_provider import get_model

@@ -20,12 +20,7 @@
 //     publishes are a whole K-half old and the reads it protects are two slices away: no drain, a counted lgkmcnt;
 //   * per K-half a wave issues 13 ds_read_b128 + 4 weight loads (+ 7 ds_write_b128 and 7 activation loads every other K-half) for 52 MFMAs.
 #pragma once
-#include <type_traits>
-#include <utility>
-#include "pcv_common.hpp"
-#include "igemm_conv.hpp"     // Mma<DT>
-#include "d3q_conv.hpp"       // D3Params, d3q_sync
-#include "d3i_conv.hpp"       // d3i_unroll
+#include "conv_device.hpp"
 
 template <int CIN_> struct D1ICfgT {
     static constexpr int THREADS = 256;
@@ -78,11 +73,11 @@ __device__ __forceinline__ void d1i_body(const D3Params& p, char* smem) {
     const uint64_t rt0__ = __builtin_amdgcn_s_memrealtime();        // 100 MHz
 #endif
 
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.x), 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w), 0, p.w_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrsrc = buffer_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t wrsrc = buffer_rsrc(p.w, p.w_bytes);
+    const __amdgpu_buffer_rsrc_t yrsrc = buffer_rsrc(p.y, p.y_bytes);
     const bool has_res = p.res != nullptr;
-    const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.res), 0, has_res ? p.res_bytes : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rrsrc = buffer_rsrc(p.res, has_res ? p.res_bytes : 0u);
 
     // ---- weights: A fragments of this wave's 64 channels, K-half kh: 4 x 1 KB at (chTile * 4 + wave) * WBYTES + kh * 4096 ----
     frag Wf[G::WRING][4];
@@ -99,7 +94,7 @@ __device__ __forceinline__ void d1i_body(const D3Params& p, char* smem) {
             Wf[sl][nb] = __builtin_bit_cast(frag, v);
         }
     };
-    d3i_unroll([&](auto KHc) __attribute__((always_inline)) { wload(decltype(KHc)::value, KHc); }, std::make_integer_sequence<int, G::PFW>{});
+    static_for<G::PFW>([&](auto KHc) __attribute__((always_inline)) { wload(decltype(KHc)::value, KHc); });
 
     // ---- activations: piece i of a thread = pixel 32 i + (tid >> 3) of the tile, 16-byte chunk tid & 7 of the slice (rows 208 .. 223 belong
     // to the next tile and are never read; pixels behind the tensor are out of range: zeros) ----
@@ -154,7 +149,7 @@ __device__ __forceinline__ void d1i_body(const D3Params& p, char* smem) {
         Pf[kh & 1][mb] = *reinterpret_cast<lds_fptr>((size_t)ab[mb] + (size_t)(((kh >> 1) % G::NS) * 128 + (kh & 1) * 64));
     };
     auto preads = [&](auto KHc) __attribute__((always_inline)) {
-        d3i_unroll([&](auto MBc) __attribute__((always_inline)) { pread(KHc, MBc); }, std::make_integer_sequence<int, NB>{});
+        static_for<NB>([&](auto MBc) __attribute__((always_inline)) { pread(KHc, MBc); });
     };
     preads(std::integral_constant<int, 0>{});
     // BN constants of the wave's two channel-block pairs: requested in place of the weight look-ahead that has nothing left to fetch
@@ -174,8 +169,7 @@ __device__ __forceinline__ void d1i_body(const D3Params& p, char* smem) {
 #pragma unroll
             for (int g = 0; g < 2; ++g) {
                 const int chl = chw + 32 * g < p.Cout ? chw + 32 * g : 0;                // pad channels: any valid entry (never stored)
-                es[g][0] = *reinterpret_cast<const f32x4*>(p.scale + chl); es[g][1] = *reinterpret_cast<const f32x4*>(p.scale + chl + 4);
-                eh[g][0] = *reinterpret_cast<const f32x4*>(p.shift + chl); eh[g][1] = *reinterpret_cast<const f32x4*>(p.shift + chl + 4);
+                load_bn8(p, chl, es[g][0], es[g][1], eh[g][0], eh[g][1]);
             }
         }
         if constexpr (ld) sload(s + 4, sb[s & 1]);
@@ -186,7 +180,7 @@ __device__ __forceinline__ void d1i_body(const D3Params& p, char* smem) {
                 acc[mb][nb] = Mma<DT>::run(Wf[(D1I_DBG & 2) ? 0 : kh % G::WRING][nb], Pf[(D1I_DBG & 1) ? 0 : (kh & 1)][mb], acc[mb][nb]);
         // issue order: four MFMAs, one fragment read; a weight load behind every third read. A K-half that writes a slice: the SPT writes one by
         // one, then the NB reads over the remaining gaps; the activation loads one by one from the first gap on.
-        d3i_unroll([&](auto MBc) __attribute__((always_inline)) {
+        static_for<NB>([&](auto MBc) __attribute__((always_inline)) {
             constexpr int mb = decltype(MBc)::value;
             __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
             if constexpr (!wr) {
@@ -199,7 +193,7 @@ __device__ __forceinline__ void d1i_body(const D3Params& p, char* smem) {
             }
             if constexpr ((mb + 1) * 4 / NB != mb * 4 / NB) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
             if constexpr (ld && mb >= NB - G::SPT) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-        }, std::make_integer_sequence<int, NB>{});
+        });
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (first && s + 1 < G::SLICES && s >= 1 && (D1I_DBG & 8) == 0) {
             // the slice's barrier: this wave's writes of slice s + 1 (a slice old) are done - behind them it has issued more LDS operations than
@@ -209,15 +203,13 @@ __device__ __forceinline__ void d1i_body(const D3Params& p, char* smem) {
             d3q_sync();
         }
     };
-    d3i_unroll([&](auto KHc) __attribute__((always_inline)) { step(KHc); }, std::make_integer_sequence<int, G::KH>{});
+    static_for<G::KH>([&](auto KHc) __attribute__((always_inline)) { step(KHc); });
 #ifdef D1I_CYCLES
     cyc__[2] = __builtin_amdgcn_s_memtime();
 #endif
 
-    // ---- epilogue: BN, activation, skip tensor, 16-byte stores (d3i_conv.hpp) ----
-    const float alo = (p.act == PCV_ACT_RELU || p.act == PCV_ACT_RELU6) ? 0.f : -INFINITY, ahi = p.act == PCV_ACT_RELU6 ? 6.f : INFINITY;
-    const float plo = (p.post_act == PCV_ACT_RELU || p.post_act == PCV_ACT_RELU6) ? 0.f : -INFINITY, phi = p.post_act == PCV_ACT_RELU6 ? 6.f : INFINITY;
-    const float clo = alo > plo ? alo : plo, chi = ahi < phi ? ahi : phi;
+    // ---- epilogue: BN, activation, skip tensor, 16-byte stores (d3i_conv.hpp; the two-value form and its dispatch: conv_device.hpp) ----
+    const EpiBounds B = make_epi_bounds(p.act, p.post_act);
     F16Guard<DT> guard;
     u32x4 rr[2][NB];
     if (has_res) {
@@ -226,7 +218,7 @@ __device__ __forceinline__ void d1i_body(const D3Params& p, char* smem) {
 #pragma unroll
             for (int mb = 0; mb < NB; ++mb) {
                 const int m = m0 + 16 * mb + fr, ch0 = chw + 32 * g;
-                const uint32_t roff = (ch0 < p.Cout && m < p.M) ? (uint32_t)((m * p.Cout + ch0) * 2) : 0x80000000u;
+                const uint32_t roff = (ch0 < p.Cout && m < p.M) ? nhwc_off(m, p.Cout, ch0) : kOutOfRange;
                 rr[g][mb] = __builtin_amdgcn_raw_buffer_load_b128(rrsrc, roff, 0, 0);
             }
     }
@@ -246,44 +238,19 @@ __device__ __forceinline__ void d1i_body(const D3Params& p, char* smem) {
                 const f32x4& sc = hf == 0 ? es0 : es1;
                 const f32x4& sh = hf == 0 ? eh0 : eh1;
                 float v0 = a[k0] * sc[k0] + sh[k0], v1 = a[k0 + 1] * sc[k0 + 1] + sh[k0 + 1];
-                if constexpr (RO) {
-                    if constexpr (HR) {
-                        float lo, hi;
-                        unpack2<DT>(rr[g][mb][e], lo, hi);
-                        v0 += lo;
-                        v1 += hi;
-                    }
-                    v0 = __builtin_elementwise_maximum(v0, 0.f);
-                    v1 = __builtin_elementwise_maximum(v1, 0.f);
-                } else if constexpr (HR) {
-                    v0 = __builtin_elementwise_minimum(__builtin_elementwise_maximum(v0, alo), ahi);
-                    v1 = __builtin_elementwise_minimum(__builtin_elementwise_maximum(v1, alo), ahi);
-                    float lo, hi;
-                    unpack2<DT>(rr[g][mb][e], lo, hi);
-                    v0 += lo;
-                    v1 += hi;
-                    v0 = __builtin_elementwise_minimum(__builtin_elementwise_maximum(v0, plo), phi);
-                    v1 = __builtin_elementwise_minimum(__builtin_elementwise_maximum(v1, plo), phi);
-                } else {
-                    v0 = __builtin_elementwise_minimum(__builtin_elementwise_maximum(v0, clo), chi);
-                    v1 = __builtin_elementwise_minimum(__builtin_elementwise_maximum(v1, clo), chi);
-                }
-                guard.see2(v0, v1);
-                o[e] = pack2<DT>(v0, v1);
+                o[e] = epi2<DT, HR, RO>(v0, v1, rr[g][mb][e], B, guard);
             }
             const int m = m0 + 16 * mb + fr;
-            const uint32_t boff = (chok && m < p.M) ? (uint32_t)((m * p.Ypitch + ch0) * 2) : 0x80000000u;     // (the host keeps y below 2 GiB)
+            const uint32_t boff = (chok && m < p.M) ? nhwc_off(m, p.Ypitch, ch0) : kOutOfRange;     // (the host keeps y below 2 GiB)
             __builtin_amdgcn_raw_buffer_store_b128(o, yrsrc, boff, 0, 0);
         }
     };
     const bool relu_only = has_res ? (p.act == PCV_ACT_NONE && p.post_act == PCV_ACT_RELU)
                                    : ((p.act == PCV_ACT_RELU && p.post_act <= PCV_ACT_RELU) || (p.act == PCV_ACT_NONE && p.post_act == PCV_ACT_RELU));
-    auto both = [&](auto HRc, auto ROc) __attribute__((always_inline)) {
+    epi_dispatch(has_res, relu_only, [&](auto HRc, auto ROc) __attribute__((always_inline)) {
         half(HRc, ROc, std::integral_constant<int, 0>{});
         half(HRc, ROc, std::integral_constant<int, 1>{});
-    };
-    if (has_res) { if (relu_only) both(std::true_type{}, std::true_type{}); else both(std::true_type{}, std::false_type{}); }
-    else { if (relu_only) both(std::false_type{}, std::true_type{}); else both(std::false_type{}, std::false_type{}); }
+    });
     guard.commit(p.ovf);
 #ifdef D1I_CYCLES
     __builtin_amdgcn_s_waitcnt(0x0070);

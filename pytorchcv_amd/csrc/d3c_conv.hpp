@@ -6,7 +6,7 @@
 //           (reference pytorchcv/models/common/conv.py:278-286) at ResBottleneck.conv2 / ResBlock.conv1, conv2 of the 56 x 56
 //           stage (resnet.py:49,56,120-127), plus the residual add + ReLU of basic-block units (resnet.py:227-228) in the
 //           epilogue. Same K order (filter row, filter column; one 64-channel slice), same MFMA sequence per accumulator, same
-//           epilogue arithmetic as d3q_conv.hpp / igemm_conv.hpp: bit-identical results.
+//           epilogue arithmetic (conv_device.hpp) as d3q_conv.hpp / igemm_conv.hpp: bit-identical results.
 //
 // Why (round 4). With 64 input and 64 output channels the general kernels are bound by the L2 -> LDS path, not by the MFMA:
 // a 64 x 448 tile pulls 27 KB per K-step (the activation rows three times - once per filter row - plus the weights) for 896
@@ -22,10 +22,7 @@
 // as everywhere); the pitch of 64 keeps R & 7 independent of the image row, so a lane's fragment address is a per-(block, filter
 // column) constant + an immediate for the filter row.
 #pragma once
-#include <type_traits>
-#include "pcv_common.hpp"
-#include "igemm_conv.hpp"     // Mma<DT>
-#include "d3q_conv.hpp"       // D3Params, D3Tiles, d3q_tiles
+#include "conv_device.hpp"
 
 struct D3CCfg {
     static constexpr int THREADS = 256;
@@ -57,11 +54,11 @@ __device__ __forceinline__ void d3c_body(const D3Params& p, char* smem) {
     const D3Tiles T = d3q_tiles(p);
     if (T.nMine == 0) return;
 
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w), 0, p.w_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.x), 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrsrc = buffer_rsrc(p.w, p.w_bytes);
+    const __amdgpu_buffer_rsrc_t xrsrc = buffer_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t yrsrc = buffer_rsrc(p.y, p.y_bytes);
     const bool has_res = p.res != nullptr;
-    const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.res), 0, has_res ? p.res_bytes : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rrsrc = buffer_rsrc(p.res, has_res ? p.res_bytes : 0u);
     const int tilesPerImage = (p.H + G::ROWS - 1) / G::ROWS;
 
     // ---- the zero columns of both patch slots (LDS rows 0 and 57..63 of every staged image row; the DMA never writes them) ----
@@ -87,8 +84,7 @@ __device__ __forceinline__ void d3c_body(const D3Params& p, char* smem) {
             }
         const int ch0 = chTile * G::BM + wc * 32 + 8 * fq;
         const int chl = ch0 < p.Cout ? ch0 : 0;                  // pad channels: any valid entry (never stored)
-        es0 = *reinterpret_cast<const f32x4*>(p.scale + chl); es1 = *reinterpret_cast<const f32x4*>(p.scale + chl + 4);
-        eh0 = *reinterpret_cast<const f32x4*>(p.shift + chl); eh1 = *reinterpret_cast<const f32x4*>(p.shift + chl + 4);
+        load_bn8(p, chl, es0, es1, eh0, eh1);
     };
 
     // ---- fragment addresses: block j, filter column q (row offset q, swizzle key (px + q) & 7); filter row r = + r * 8192 bytes ----
@@ -113,7 +109,7 @@ __device__ __forceinline__ void d3c_body(const D3Params& p, char* smem) {
     uint32_t vt = 0x80000000u;                                    // the next tile's offset of piece 0 (2^31: no next tile - zeros into the free slot)
     __amdgpu_buffer_rsrc_t xr = xrsrc;
     auto dma_setup = [&](bool more, int n, int y0) __attribute__((always_inline)) {
-        xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(p.x)) + (size_t)n * imgBytes, 0, imgBytes, 0x00020000);
+        xr = buffer_rsrc(reinterpret_cast<const char*>(p.x) + (size_t)n * imgBytes, imgBytes);
         vt = more ? lanesrc + (uint32_t)((y0 - 1) * (G::W * 128)) : 0x80000000u;
     };
     auto dma_piece = [&](auto Ic, int slot) __attribute__((always_inline)) {
@@ -126,12 +122,7 @@ __device__ __forceinline__ void d3c_body(const D3Params& p, char* smem) {
         const uint32_t voff = real ? vt + (uint32_t)(I * 4096) : 0x80000000u;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (lds_char*)(size_t)dst, 16, voff, 0, 0, 0);
     };
-    auto tile_pos = [&](int t, int& chTile, int& n, int& y0) __attribute__((always_inline)) {
-        chTile = t % p.nChTiles;
-        const int pt = t / p.nChTiles;
-        n = pt / tilesPerImage;
-        y0 = (pt - n * tilesPerImage) * G::ROWS;
-    };
+    auto tile_pos = [&](int t, int& chTile, int& n, int& y0) __attribute__((always_inline)) { d3r_tile_pos<G::ROWS>(p, tilesPerImage, t, chTile, n, y0); };
 
     // K loop order: PIXEL BLOCK outer, K-half inner. A block's two accumulators (its 16 pixels x this wave's 32 channels) run
     // through all 18 K-halves (36 MFMAs; a 16x16x32 chain on one accumulator issues at the full rate), then the block is
@@ -148,14 +139,10 @@ __device__ __forceinline__ void d3c_body(const D3Params& p, char* smem) {
         const uint32_t a = bs[j][q] ^ (uint32_t)(h << 6);                           // (kc + 4) ^ key = (kc ^ key) ^ 4: bit 6 of the address
         bq[st % RING] = *reinterpret_cast<lds_fptr>((size_t)a + (size_t)(r * G::PITCH * 128));
     };
-    // Activations none / ReLU / ReLU6 as BRANCH-FREE clamps to launch-uniform bounds (-inf / 0, +inf / 6; IEEE-754-2019 maximum /
-    // minimum: a NaN stays a NaN, max(v, -inf) = v and min(v, +inf) = v bit for bit): the uniform switch of `clampn` is a dozen scalar
-    // branches per pixel block, and a wave that is alone on its SIMD pays every one of them (3 100 cycles per tile's epilogue).
-    const float alo = (p.act == PCV_ACT_RELU || p.act == PCV_ACT_RELU6) ? 0.f : -INFINITY, ahi = p.act == PCV_ACT_RELU6 ? 6.f : INFINITY;
-    const float plo = (p.post_act == PCV_ACT_RELU || p.post_act == PCV_ACT_RELU6) ? 0.f : -INFINITY, phi = p.post_act == PCV_ACT_RELU6 ? 6.f : INFINITY;
-    const float clo = alo > plo ? alo : plo, chi = ahi < phi ? ahi : phi;
+    // activations none / ReLU / ReLU6 as branch-free clamps to launch-uniform bounds (conv_device.hpp)
+    const EpiBounds B = make_epi_bounds(p.act, p.post_act);
     // One pixel block's epilogue, in FOUR parts of two values each (v = acc * scale + shift -> act -> (+ residual) -> post_act ->
-    // packed pair; d3q_conv.hpp) + the 16-byte NHWC store. The parts of block j - 1 are written BETWEEN the steps of block j (its
+    // packed pair: epi2, conv_device.hpp) + the 16-byte NHWC store. The parts of block j - 1 are written BETWEEN the steps of block j (its
     // accumulator pair is the other one), so that the vector ALU work sits under the next block's MFMAs in program order too - left
     // to the scheduler, a block's epilogue ran as one run of ~45 VALU instructions behind its last MFMA, the matrix pipe idle.
     u32x4 rrq[7];                                                 // the tile's residual pieces (requested at the tile's start)
@@ -167,27 +154,11 @@ __device__ __forceinline__ void d3c_body(const D3Params& p, char* smem) {
         const f32x4& sc = half == 0 ? es0 : es1;
         const f32x4& sh = half == 0 ? eh0 : eh1;
         float v0 = cacc[j & 1][half][k0] * sc[k0] + sh[k0], v1 = cacc[j & 1][half][k0 + 1] * sc[k0 + 1] + sh[k0 + 1];
-        if constexpr (HR) {
-            v0 = __builtin_elementwise_minimum(__builtin_elementwise_maximum(v0, alo), ahi);
-            v1 = __builtin_elementwise_minimum(__builtin_elementwise_maximum(v1, alo), ahi);
-            float lo, hi;
-            unpack2<DT>(rrq[j][e], lo, hi);
-            v0 += lo;
-            v1 += hi;
-            v0 = __builtin_elementwise_minimum(__builtin_elementwise_maximum(v0, plo), phi);
-            v1 = __builtin_elementwise_minimum(__builtin_elementwise_maximum(v1, plo), phi);
-        } else {
-            // nothing between the two activations: clamp(clamp(v, alo, ahi), plo, phi) = clamp(v, max(alo, plo), min(ahi, phi)) for
-            // these bounds (0 / -inf below, 6 / +inf above), NaN and signed zero included
-            v0 = __builtin_elementwise_minimum(__builtin_elementwise_maximum(v0, clo), chi);
-            v1 = __builtin_elementwise_minimum(__builtin_elementwise_maximum(v1, clo), chi);
-        }
-        guard.see2(v0, v1);
-        opend[e] = pack2<DT>(v0, v1);
+        opend[e] = epi2<DT, HR, false>(v0, v1, rrq[j][e], B, guard);
     };
     auto epi_store = [&](int j, int ch0, int mTile, int mEnd) __attribute__((always_inline)) {
         const int m = mTile + wp * 112 + 16 * j + fr;
-        const uint32_t boff = (ch0 < p.Cout && m < mEnd) ? (uint32_t)((m * p.Ypitch + ch0) * 2) : 0x80000000u;     // (the host keeps y below 2 GiB)
+        const uint32_t boff = (ch0 < p.Cout && m < mEnd) ? nhwc_off(m, p.Ypitch, ch0) : kOutOfRange;     // (the host keeps y below 2 GiB)
         __builtin_amdgcn_raw_buffer_store_b128(opend, yrsrc, boff, 0, 0);
     };
     // one tile: 126 steps; the 11 pieces of the NEXT tile's patch go out at steps 4, 15, 26, ... (into the other slot: every wave left
@@ -201,7 +172,7 @@ __device__ __forceinline__ void d3c_body(const D3Params& p, char* smem) {
 #pragma unroll
             for (int j = 0; j < 7; ++j) {
                 const int m = mTile + wp * 112 + 16 * j + fr;
-                const uint32_t roff = (ch0 < p.Cout && m < mEnd) ? (uint32_t)((m * p.Cout + ch0) * 2) : 0x80000000u;
+                const uint32_t roff = (ch0 < p.Cout && m < mEnd) ? nhwc_off(m, p.Cout, ch0) : kOutOfRange;
                 rrq[j] = __builtin_amdgcn_raw_buffer_load_b128(rrsrc, roff, 0, 0);
             }
         }

@@ -22,11 +22,7 @@
 // LDS image: slot (gy, gx) = pixel (gy - 1, gx - 1), byte 528 (16 gy + gx) + 2 c for channel c. Three more grid rows behind the image are
 // allocated so that the fragment reads issued ahead of the last K-half (filter row "3") stay inside the allocation.
 #pragma once
-#include <type_traits>
-#include <utility>
-#include "pcv_common.hpp"
-#include "igemm_conv.hpp"     // Mma<DT>
-#include "d3q_conv.hpp"       // D3Params, d3q_sync
+#include "conv_device.hpp"
 
 // CIN = 512 (ResNet stage 4: 7 x 7 maps, three layers of ResNet-50, three to five of ResNet-18 / 34): the same kernel with TWO images per block,
 // stacked in one 17 x 9 grid that shares the zero row between them (153 slots of 1 040 bytes = 159 KB); 98 pixels = 7 pixel blocks per
@@ -73,9 +69,6 @@ typedef D3ICfgT<256> D3ICfg;
 #endif
 
 #if defined(__HIP_DEVICE_COMPILE__)
-// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>), in order
-template <class F, int... I> __device__ __forceinline__ void d3i_unroll(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-
 template <int DT, int CIN>
 __device__ __forceinline__ void d3i_body(const D3Params& p, char* smem) {
     typedef D3ICfgT<CIN> G;
@@ -97,12 +90,11 @@ __device__ __forceinline__ void d3i_body(const D3Params& p, char* smem) {
 #endif
 
     const uint32_t imgBytes = (uint32_t)(HW * G::CIN * 2);
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(p.x)) + (size_t)n * imgBytes, 0,
-                                                                           (uint32_t)(NP * G::CIN * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w), 0, p.w_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrsrc = buffer_rsrc(reinterpret_cast<const char*>(p.x) + (size_t)n * imgBytes, (uint32_t)(NP * G::CIN * 2));
+    const __amdgpu_buffer_rsrc_t wrsrc = buffer_rsrc(p.w, p.w_bytes);
+    const __amdgpu_buffer_rsrc_t yrsrc = buffer_rsrc(p.y, p.y_bytes);
     const bool has_res = p.res != nullptr;
-    const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.res), 0, has_res ? p.res_bytes : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rrsrc = buffer_rsrc(p.res, has_res ? p.res_bytes : 0u);
 
     // ---- weights: A fragments of this wave's 64 channels, K-half kh: 4 x 1 KB at (chTile * 4 + wave) * WBYTES + kh * 4096 ----
     frag Wf[G::WRING][4];
@@ -203,7 +195,7 @@ __device__ __forceinline__ void d3i_body(const D3Params& p, char* smem) {
         Pf[j & 1][mb] = *reinterpret_cast<lds_fptr>((size_t)ab[mb] + (size_t)G::pimm(j));
     };
     auto preads = [&](auto Jc) __attribute__((always_inline)) {
-        d3i_unroll([&](auto MBc) __attribute__((always_inline)) { pread(Jc, MBc); }, std::make_integer_sequence<int, NB>{});
+        static_for<NB>([&](auto MBc) __attribute__((always_inline)) { pread(Jc, MBc); });
     };
     preads(std::integral_constant<int, 0>{});
     // BN constants of the wave's two channel-block pairs: requested in the last three K-halves, in place of the weight look-ahead that has
@@ -228,8 +220,7 @@ __device__ __forceinline__ void d3i_body(const D3Params& p, char* smem) {
 #pragma unroll
             for (int g = 0; g < 2; ++g) {
                 const int chl = chw + 32 * g < p.Cout ? chw + 32 * g : 0;                // pad channels: any valid entry (never stored)
-                es[g][0] = *reinterpret_cast<const f32x4*>(p.scale + chl); es[g][1] = *reinterpret_cast<const f32x4*>(p.scale + chl + 4);
-                eh[g][0] = *reinterpret_cast<const f32x4*>(p.shift + chl); eh[g][1] = *reinterpret_cast<const f32x4*>(p.shift + chl + 4);
+                load_bn8(p, chl, es[g][0], es[g][1], eh[g][0], eh[g][1]);
             }
         }
         if constexpr (sf > 0) sload(sf, sb[sf % G::SBUF]);
@@ -240,7 +231,7 @@ __device__ __forceinline__ void d3i_body(const D3Params& p, char* smem) {
                 acc[mb][nb] = Mma<DT>::run(Wf[(D3I_DBG & 2) ? 0 : j % G::WRING][nb], Pf[(D3I_DBG & 1) ? 0 : (j & 1)][mb], acc[mb][nb]);
         // issue order: four MFMAs, one fragment read; a weight load behind every third read; a staging load behind each of the first SPT.
         // A K-half that writes a slice: the SPT writes one by one, then the NB reads over the remaining gaps.
-        d3i_unroll([&](auto MBc) __attribute__((always_inline)) {
+        static_for<NB>([&](auto MBc) __attribute__((always_inline)) {
             constexpr int mb = decltype(MBc)::value;
             __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
             if constexpr (sw == 0) {
@@ -253,7 +244,7 @@ __device__ __forceinline__ void d3i_body(const D3Params& p, char* smem) {
             }
             if constexpr ((mb + 1) * 4 / NB != mb * 4 / NB) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
             if constexpr (sf > 0 && mb < G::SPT) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-        }, std::make_integer_sequence<int, NB>{});
+        });
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (sw > 0) {                                       // every wave's pieces of slice sw are in LDS before anybody requests its fragments (two K-halves on)
             __builtin_amdgcn_s_waitcnt(0xc07f);                       // lgkmcnt(0)
@@ -261,7 +252,7 @@ __device__ __forceinline__ void d3i_body(const D3Params& p, char* smem) {
         }
     };
     auto row = [&](auto Rc) __attribute__((always_inline)) {
-        d3i_unroll([&](auto Jc) __attribute__((always_inline)) { step(Rc, Jc); }, std::make_integer_sequence<int, G::JR>{});
+        static_for<G::JR>([&](auto Jc) __attribute__((always_inline)) { step(Rc, Jc); });
 #pragma unroll
         for (int mb = 0; mb < NB; ++mb) ab[mb] += (uint32_t)G::ROWB;
 #ifdef D3I_CYCLES
@@ -274,9 +265,7 @@ __device__ __forceinline__ void d3i_body(const D3Params& p, char* smem) {
 
     // ---- epilogue: BN, activation, skip tensor, 16-byte stores. Lane (fr, fq) of channel-block pair g holds channels c0 .. c0 + 7 of pixel
     // 16 mb + fr: blocks 2 g (c0 + 0..3) and 2 g + 1 (c0 + 4..7) in the packed row order. ----
-    const float alo = (p.act == PCV_ACT_RELU || p.act == PCV_ACT_RELU6) ? 0.f : -INFINITY, ahi = p.act == PCV_ACT_RELU6 ? 6.f : INFINITY;
-    const float plo = (p.post_act == PCV_ACT_RELU || p.post_act == PCV_ACT_RELU6) ? 0.f : -INFINITY, phi = p.post_act == PCV_ACT_RELU6 ? 6.f : INFINITY;
-    const float clo = alo > plo ? alo : plo, chi = ahi < phi ? ahi : phi;
+    const EpiBounds B = make_epi_bounds(p.act, p.post_act);
     const int mImg = n * HW;
     F16Guard<DT> guard;
     // the skip tensor's 26 pieces of this lane, all requested up front (the fragment and weight registers are free now): one exposed HBM
@@ -288,12 +277,11 @@ __device__ __forceinline__ void d3i_body(const D3Params& p, char* smem) {
 #pragma unroll
             for (int mb = 0; mb < NB; ++mb) {
                 const int pix = 16 * mb + fr, ch0 = chw + 32 * g;
-                const uint32_t roff = (ch0 < p.Cout && pix < NP) ? (uint32_t)(((mImg + pix) * p.Cout + ch0) * 2) : 0x80000000u;
+                const uint32_t roff = (ch0 < p.Cout && pix < NP) ? nhwc_off(mImg + pix, p.Cout, ch0) : kOutOfRange;
                 rr[g][mb] = __builtin_amdgcn_raw_buffer_load_b128(rrsrc, roff, 0, 0);
             }
     }
-    // ROc: the ResNet forms - ReLU only (no skip tensor), or no activation + skip tensor + ReLU - as one v_maximum3 per value; the general form
-    // clamps to launch-uniform bounds (two instructions per clamp, infinite bounds included). Same values either way.
+    // HRc: a skip tensor; ROc: the ReLU-only ResNet forms (epi2 / epi_dispatch, conv_device.hpp)
     auto half = [&](auto HRc, auto ROc, auto Gc) __attribute__((always_inline)) {
         constexpr bool HR = decltype(HRc)::value, RO = decltype(ROc)::value;
         constexpr int g = decltype(Gc)::value;
@@ -310,44 +298,19 @@ __device__ __forceinline__ void d3i_body(const D3Params& p, char* smem) {
                 const f32x4& sc = hf == 0 ? es0 : es1;
                 const f32x4& sh = hf == 0 ? eh0 : eh1;
                 float v0 = a[k0] * sc[k0] + sh[k0], v1 = a[k0 + 1] * sc[k0 + 1] + sh[k0 + 1];
-                if constexpr (RO) {
-                    if constexpr (HR) {
-                        float lo, hi;
-                        unpack2<DT>(rr[g][mb][e], lo, hi);
-                        v0 += lo;
-                        v1 += hi;
-                    }
-                    v0 = __builtin_elementwise_maximum(v0, 0.f);
-                    v1 = __builtin_elementwise_maximum(v1, 0.f);
-                } else if constexpr (HR) {
-                    v0 = __builtin_elementwise_minimum(__builtin_elementwise_maximum(v0, alo), ahi);
-                    v1 = __builtin_elementwise_minimum(__builtin_elementwise_maximum(v1, alo), ahi);
-                    float lo, hi;
-                    unpack2<DT>(rr[g][mb][e], lo, hi);
-                    v0 += lo;
-                    v1 += hi;
-                    v0 = __builtin_elementwise_minimum(__builtin_elementwise_maximum(v0, plo), phi);
-                    v1 = __builtin_elementwise_minimum(__builtin_elementwise_maximum(v1, plo), phi);
-                } else {
-                    v0 = __builtin_elementwise_minimum(__builtin_elementwise_maximum(v0, clo), chi);
-                    v1 = __builtin_elementwise_minimum(__builtin_elementwise_maximum(v1, clo), chi);
-                }
-                guard.see2(v0, v1);
-                o[e] = pack2<DT>(v0, v1);
+                o[e] = epi2<DT, HR, RO>(v0, v1, rr[g][mb][e], B, guard);
             }
             const int pix = 16 * mb + fr;
-            const uint32_t boff = (chok && pix < NP) ? (uint32_t)(((mImg + pix) * p.Ypitch + ch0) * 2) : 0x80000000u;     // (the host keeps y below 2 GiB)
+            const uint32_t boff = (chok && pix < NP) ? nhwc_off(mImg + pix, p.Ypitch, ch0) : kOutOfRange;     // (the host keeps y below 2 GiB)
             __builtin_amdgcn_raw_buffer_store_b128(o, yrsrc, boff, 0, 0);
         }
     };
     const bool relu_only = has_res ? (p.act == PCV_ACT_NONE && p.post_act == PCV_ACT_RELU)
                                    : ((p.act == PCV_ACT_RELU && p.post_act <= PCV_ACT_RELU) || (p.act == PCV_ACT_NONE && p.post_act == PCV_ACT_RELU));
-    auto both = [&](auto HRc, auto ROc) __attribute__((always_inline)) {
+    epi_dispatch(has_res, relu_only, [&](auto HRc, auto ROc) __attribute__((always_inline)) {
         half(HRc, ROc, std::integral_constant<int, 0>{});
         half(HRc, ROc, std::integral_constant<int, 1>{});
-    };
-    if (has_res) { if (relu_only) both(std::true_type{}, std::true_type{}); else both(std::true_type{}, std::false_type{}); }
-    else { if (relu_only) both(std::false_type{}, std::true_type{}); else both(std::false_type{}, std::false_type{}); }
+    });
     guard.commit(p.ovf);
 #ifdef D3I_CYCLES
     __builtin_amdgcn_s_waitcnt(0x0070);

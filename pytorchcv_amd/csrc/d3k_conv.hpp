@@ -20,10 +20,7 @@
 // LDS image: [slot][slice][staged row][32 rows x 128 B]; LDS row u of an image row holds pixel u - 1; 16-byte chunk slot s of LDS row R holds
 // K-chunk s ^ (R & 7).
 #pragma once
-#include <type_traits>
-#include "pcv_common.hpp"
-#include "igemm_conv.hpp"     // Mma<DT>
-#include "d3q_conv.hpp"       // D3Params, D3Tiles, d3q_tiles
+#include "conv_device.hpp"
 
 struct D3KCfg {
     static constexpr int THREADS = 256;
@@ -85,10 +82,10 @@ __device__ __forceinline__ void d3k_body(const D3Params& p, char* smem) {
     const D3Tiles T = d3q_tiles(p);
     if (T.nMine == 0) return;
 
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w), 0, p.w_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrsrc = buffer_rsrc(p.w, p.w_bytes);
+    const __amdgpu_buffer_rsrc_t yrsrc = buffer_rsrc(p.y, p.y_bytes);
     const bool has_res = p.res != nullptr;
-    const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.res), 0, has_res ? p.res_bytes : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rrsrc = buffer_rsrc(p.res, has_res ? p.res_bytes : 0u);
     const int tilesPerImage = (p.H + G::ROWS - 1) / G::ROWS;
 
     // ---- LDS row 0 of every staged row (pixel -1: the left padding) in both slots; the DMA never writes it. Rows 29..31 (and row 0 of the
@@ -113,8 +110,7 @@ __device__ __forceinline__ void d3k_body(const D3Params& p, char* smem) {
             }
         const int ch0 = chTile * G::BM + wave * 32 + 8 * fq;
         const int chl = ch0 < p.Cout ? ch0 : 0;                  // pad channels: any valid entry (never stored)
-        es0 = *reinterpret_cast<const f32x4*>(p.scale + chl); es1 = *reinterpret_cast<const f32x4*>(p.scale + chl + 4);
-        eh0 = *reinterpret_cast<const f32x4*>(p.shift + chl); eh1 = *reinterpret_cast<const f32x4*>(p.shift + chl + 4);
+        load_bn8(p, chl, es0, es1, eh0, eh1);
     };
 
     // ---- fragment addresses: block j, filter column q (row offset q, swizzle key (px + q) & 7); filter row r = + r * 4096, slice = + 24576 ----
@@ -135,9 +131,9 @@ __device__ __forceinline__ void d3k_body(const D3Params& p, char* smem) {
     const uint32_t lanesrc = (wave == 3 && lrow >= 4) ? 0x80000000u
                                                       : (uint32_t)((8 * wave + lrow) * (G::CIN * 2) + (((lane & 7) ^ ((1 + lrow) & 7)) << 4));
     uint32_t vt = 0x80000000u;                                    // the next tile's offset of piece 0 (2^31: no next tile - zeros into the free slot)
-    __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.x), 0, 0, 0x00020000);
+    __amdgpu_buffer_rsrc_t xr = buffer_rsrc(p.x, 0);
     auto dma_setup = [&](bool more, int n, int y0) __attribute__((always_inline)) {
-        xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(p.x)) + (size_t)n * imgBytes, 0, imgBytes, 0x00020000);
+        xr = buffer_rsrc(reinterpret_cast<const char*>(p.x) + (size_t)n * imgBytes, imgBytes);
         vt = (more && lanesrc != 0x80000000u) ? lanesrc + (uint32_t)((y0 - 1) * (G::W * G::CIN * 2)) : 0x80000000u;
     };
     auto dma_piece = [&](auto Ic, int slot) __attribute__((always_inline)) {
@@ -146,12 +142,7 @@ __device__ __forceinline__ void d3k_body(const D3Params& p, char* smem) {
         // (a row above the image: y0 - 1 + ry = -1 wraps below zero = beyond num_records; the 2^31 marker stays beyond it under these adds)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (lds_char*)(size_t)dst, 16, vt + (uint32_t)(ry * (G::W * G::CIN * 2) + sl * 128), 0, 0, 0);
     };
-    auto tile_pos = [&](int t, int& chTile, int& n, int& y0) __attribute__((always_inline)) {
-        chTile = t % p.nChTiles;
-        const int pt = t / p.nChTiles;
-        n = pt / tilesPerImage;
-        y0 = (pt - n * tilesPerImage) * G::ROWS;
-    };
+    auto tile_pos = [&](int t, int& chTile, int& n, int& y0) __attribute__((always_inline)) { d3r_tile_pos<G::ROWS>(p, tilesPerImage, t, chTile, n, y0); };
 
     // K loop order: PIXEL BLOCK outer, K-half inner (d3c_conv.hpp): a block's two accumulators run through all 36 K-halves (72 MFMAs), then
     // the block is finished and stored while the next block's MFMAs run. One fragment read per step, RD steps ahead.
@@ -165,10 +156,8 @@ __device__ __forceinline__ void d3k_body(const D3Params& p, char* smem) {
         const uint32_t a = bs[j][q] ^ (uint32_t)(h << 6);                           // (kc + 4) ^ key = (kc ^ key) ^ 4: bit 6 of the address
         bq[st % RING] = *reinterpret_cast<lds_fptr>((size_t)a + (size_t)(r * G::ROWB + sl * G::SLICEB));
     };
-    // activations none / ReLU / ReLU6 as branch-free clamps to launch-uniform bounds (d3c_conv.hpp)
-    const float alo = (p.act == PCV_ACT_RELU || p.act == PCV_ACT_RELU6) ? 0.f : -INFINITY, ahi = p.act == PCV_ACT_RELU6 ? 6.f : INFINITY;
-    const float plo = (p.post_act == PCV_ACT_RELU || p.post_act == PCV_ACT_RELU6) ? 0.f : -INFINITY, phi = p.post_act == PCV_ACT_RELU6 ? 6.f : INFINITY;
-    const float clo = alo > plo ? alo : plo, chi = ahi < phi ? ahi : phi;
+    // activations none / ReLU / ReLU6 as branch-free clamps to launch-uniform bounds (conv_device.hpp)
+    const EpiBounds B = make_epi_bounds(p.act, p.post_act);
     u32x4 rrq[NB];                                                // the tile's residual pieces (requested at the tile's start)
     u32x4 opend;                                                  // the packed outputs of the block being finished
     auto epi_part = [&](auto HRc, auto Jc, auto Ec, F16Guard<DT>& guard) __attribute__((always_inline)) {
@@ -178,25 +167,11 @@ __device__ __forceinline__ void d3k_body(const D3Params& p, char* smem) {
         const f32x4& sc = half == 0 ? es0 : es1;
         const f32x4& sh = half == 0 ? eh0 : eh1;
         float v0 = cacc[j & 1][half][k0] * sc[k0] + sh[k0], v1 = cacc[j & 1][half][k0 + 1] * sc[k0 + 1] + sh[k0 + 1];
-        if constexpr (HR) {
-            v0 = __builtin_elementwise_minimum(__builtin_elementwise_maximum(v0, alo), ahi);
-            v1 = __builtin_elementwise_minimum(__builtin_elementwise_maximum(v1, alo), ahi);
-            float lo, hi;
-            unpack2<DT>(rrq[j][e], lo, hi);
-            v0 += lo;
-            v1 += hi;
-            v0 = __builtin_elementwise_minimum(__builtin_elementwise_maximum(v0, plo), phi);
-            v1 = __builtin_elementwise_minimum(__builtin_elementwise_maximum(v1, plo), phi);
-        } else {
-            v0 = __builtin_elementwise_minimum(__builtin_elementwise_maximum(v0, clo), chi);
-            v1 = __builtin_elementwise_minimum(__builtin_elementwise_maximum(v1, clo), chi);
-        }
-        guard.see2(v0, v1);
-        opend[e] = pack2<DT>(v0, v1);
+        opend[e] = epi2<DT, HR, false>(v0, v1, rrq[j][e], B, guard);
     };
     auto epi_store = [&](int j, int ch0, int mTile, int mEnd) __attribute__((always_inline)) {
         const int m = mTile + 16 * j + fr;
-        const uint32_t boff = (ch0 < p.Cout && m < mEnd) ? (uint32_t)((m * p.Ypitch + ch0) * 2) : 0x80000000u;     // (the host keeps y below 2 GiB)
+        const uint32_t boff = (ch0 < p.Cout && m < mEnd) ? nhwc_off(m, p.Ypitch, ch0) : kOutOfRange;     // (the host keeps y below 2 GiB)
         __builtin_amdgcn_raw_buffer_store_b128(opend, yrsrc, boff, 0, 0);
     };
     // one tile: 252 steps; the 12 pieces of the NEXT tile's patch go out every 20 steps from step 4 (into the other slot: every wave left it
@@ -209,7 +184,7 @@ __device__ __forceinline__ void d3k_body(const D3Params& p, char* smem) {
 #pragma unroll
             for (int j = 0; j < NB; ++j) {
                 const int m = mTile + 16 * j + fr;
-                const uint32_t roff = (ch0 < p.Cout && m < mEnd) ? (uint32_t)((m * p.Cout + ch0) * 2) : 0x80000000u;
+                const uint32_t roff = (ch0 < p.Cout && m < mEnd) ? nhwc_off(m, p.Cout, ch0) : kOutOfRange;
                 rrq[j] = __builtin_amdgcn_raw_buffer_load_b128(rrsrc, roff, 0, 0);
             }
         }

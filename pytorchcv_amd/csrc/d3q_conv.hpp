@@ -40,36 +40,7 @@
 //   WAR  every fragment read is retired (lgkmcnt(0)) before the barrier that ends its interval; the A slot of K-step k - 1
 //        and the B slot of group g - 1 are re-filled from K-step k / 3 g on, after both groups' last reads of them.
 #pragma once
-#include <type_traits>
-#include "pcv_common.hpp"
-#include "igemm_conv.hpp"     // Mma<DT>, FastDiv
-
-struct D3Params {
-    const void* x;          // NHWC [N,H,W,Cin], dense
-    const void* w;          // packed weights [rows][Kpad], K = (r, slice, q), rows in MFMA order
-    const void* res;        // residual NHWC [M, Cout] or null
-    void* y;                // NHWC [M, Ypitch]
-    const float* scale;     // [Cout] fp32, never null
-    const float* shift;
-    uint32_t x_bytes, w_bytes, y_bytes, res_bytes;
-    int M;                  // N*H*W
-    int Cout, Ypitch;
-    int H, W, Cin, HW;
-    FastDiv div_hw, div_w;
-    int nk;                 // K-steps = 9 * Cin / 64 (a multiple of 3)
-    int slices;             // Cin / 64
-    int Kpad;
-    int act, post_act;
-    int nChTiles, nTiles;
-    uint32_t* dbg;          // diagnostic builds only (-DD3X3_STAMPS)
-    int stride, Hin, Win;   // 1x1 mode only: output pixel (n, ho, wo) reads input pixel (n, stride ho, stride wo) of an Hin x Win map
-                            // (H, W, HW, div_hw, div_w then describe the OUTPUT map)
-    uint32_t* ovf;          // the context's fp16 overflow counter (pcv_common.hpp, F16Guard)
-    int tailN;              // p1r_conv.hpp only: tiles nTiles .. nTiles + tailN - 1 are split into 16-pixel units over the blocks (0: none)
-    int dbgflags;           // timing experiments only (pcv_set_tuning("dbg", bits); results are WRONG with any bit set): 1 = output stores
-                            // dropped (out-of-range offsets), 2 = no epilogue at all, 4 = loaders keep the first tile's row table, 8 = compute waves keep the
-                            // first tile's column masks, 16 = row table built at the tile change (A/B of the look-ahead build; results stay right)
-};
+#include "conv_device.hpp"
 
 // In-kernel stamps (cdna_hip_programming.md section 7): a diagnostic build (-DD3X3_STAMPS) times ONE section per K-step - the
 // stamp that opens it and the stamp that closes it, s_memtime low words written into the lanes of one VGPR per wave - and
@@ -140,26 +111,6 @@ template <int WC, int WP, int CBW, int PBW, int KS, bool ONE = false> struct D3C
 };
 
 #if defined(__HIP_DEVICE_COMPILE__)
-// The tile list of a block: [tile0, tend) of its XCD's contiguous range, stride = blocks per XCD (every wave computes the same).
-struct D3Tiles {
-    int tile0, tend, tstride, nMine;
-};
-__device__ __forceinline__ D3Tiles d3q_tiles(const D3Params& p) {
-    D3Tiles t;
-    const int perXcd = (p.nTiles + 7) >> 3;
-    const int xcd = blockIdx.x & 7;
-    t.tstride = gridDim.x >> 3;                               // host guarantees gridDim.x % 8 == 0
-    t.tile0 = xcd * perXcd + (int)(blockIdx.x >> 3);
-    t.tend = min(p.nTiles, (xcd + 1) * perXcd);
-    t.nMine = t.tile0 < t.tend ? (t.tend - t.tile0 + t.tstride - 1) / t.tstride : 0;
-    return t;
-}
-__device__ __forceinline__ void d3q_sync() {
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-}
-
 // ---- loader wave lw (0..3): every LDS-DMA piece of the block ------------------------------------------------------------------------
 template <int DT, int WC, int WP, int CBW, int PBW, int KS, bool ONE>
 __device__ __forceinline__ void d3q_loader(const D3Params& p, char* smem, const int lw) {
@@ -175,15 +126,14 @@ __device__ __forceinline__ void d3q_loader(const D3Params& p, char* smem, const 
     const int nk = p.nk;
     const int K_total = T.nMine * nk, G_total = ONE ? K_total : T.nMine * (nk / 3);
 
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w), 0, p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrsrc = buffer_rsrc(p.w, p.w_bytes);
     // Activations: the descriptor's base sits one image row BELOW x, so that the (wave-uniform, unsigned) scalar offset of a
     // group, (r * W * Cin + 64 c) elements, reaches the row above a pixel with r = 0. num_records covers the per-lane offset
     // of any pixel plus the largest scalar offset (whether or not the range check adds the scalar offset, a valid lane passes
     // it); a row that must read as zeros gets the offset 2^31, beyond num_records either way (the host keeps
     // x_bytes + 2 rows below 2^31).
     const uint32_t rowBytes = ONE ? 0u : (uint32_t)(p.W * p.Cin * 2);
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char*>(reinterpret_cast<const char*>(p.x)) - rowBytes, 0, p.x_bytes + 2u * rowBytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrsrc = buffer_rsrc(reinterpret_cast<const char*>(p.x) - rowBytes, p.x_bytes + 2u * rowBytes);
 
     // weights: K-step `la_k` of tile `la_tile` goes to A slot la_slot; loader lw owns pieces NL i + lw (rows 8 (NL i + lw) + lrow)
     int la_tile = T.tile0, la_k = 0, la_slot = 0, la_g = 0;    // la_g: global index of the next K-step to issue
@@ -399,9 +349,9 @@ __device__ __forceinline__ void d3q_body(const D3Params& p, char* smem, const in
     const int nk = p.nk;
     const int K_total = T.nMine * nk;                         // K-steps this block walks
 
-    const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t yrsrc = buffer_rsrc(p.y, p.y_bytes);
     const __amdgpu_buffer_rsrc_t rrsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.res), 0, p.res != nullptr ? p.res_bytes : 0u, 0x00020000);
+        buffer_rsrc(p.res, p.res != nullptr ? p.res_bytes : 0u);
 
     f32x4 acc[CBW][PBW];
     frag a[KS][CBW], b[KS][PBW];
@@ -477,8 +427,8 @@ __device__ __forceinline__ void d3q_body(const D3Params& p, char* smem, const in
     // every fragment read of this wave has returned (a compiler-visible wait: lgkmcnt(0), the other counters untouched)
     auto reads_done = [&]() __attribute__((always_inline)) { __builtin_amdgcn_s_waitcnt(0xC07F); };
 
-    // Epilogue: v = acc * scale + shift -> act -> (+ residual) -> post_act -> one 16-byte NHWC store per (channel pair, pixel
-    // block). Branch-free: pad channels / rows past the tile read clamped table entries and an out-of-range (zero) residual and
+    // Epilogue (its steps: conv_device.hpp): v = acc * scale + shift -> act -> (+ residual) -> post_act -> one 16-byte NHWC store per
+    // (channel pair, pixel block). Branch-free: pad channels / rows past the tile read clamped table entries and an out-of-range (zero) residual and
     // are dropped by the store's range check. Activations: none / ReLU / ReLU6 only (the host sends anything else to the generic
     // kernel) - one inlined copy of this code per wave group.
     // Packed weight row (16 i + rho) of a 64-row group holds channel 32 (i >> 1) + 8 (rho >> 2) + 4 (i & 1) + (rho & 3): lane group
@@ -496,8 +446,7 @@ __device__ __forceinline__ void d3q_body(const D3Params& p, char* smem, const in
         for (int ip = 0; ip < CBW / 2; ++ip) {
             const int ch0 = chTile * BM + wc * 16 * CBW + 32 * ip + 8 * fq;
             const int chl = ch0 < p.Cout ? ch0 : 0;              // table index of a pad channel: any valid one (never stored)
-            es0[ip] = *reinterpret_cast<const f32x4*>(p.scale + chl); es1[ip] = *reinterpret_cast<const f32x4*>(p.scale + chl + 4);
-            eh0[ip] = *reinterpret_cast<const f32x4*>(p.shift + chl); eh1[ip] = *reinterpret_cast<const f32x4*>(p.shift + chl + 4);
+            load_bn8(p, chl, es0[ip], es1[ip], eh0[ip], eh1[ip]);
         }
     };
     auto epilogue = [&](int t) __attribute__((always_inline)) {
@@ -518,7 +467,7 @@ __device__ __forceinline__ void d3q_body(const D3Params& p, char* smem, const in
 #pragma unroll
                 for (int j = 0; j < PBW; ++j) {
                     const int m = mBase + 16 * j;
-                    const uint32_t roff = (chok && m < p.M) ? (uint32_t)(((size_t)m * p.Cout + ch0) * 2) : 0x80000000u;
+                    const uint32_t roff = (chok && m < p.M) ? nhwc_off((size_t)m, p.Cout, ch0) : kOutOfRange;
                     rr[j] = __builtin_amdgcn_raw_buffer_load_b128(rrsrc, roff, 0, 0);
                 }
             }
@@ -526,26 +475,16 @@ __device__ __forceinline__ void d3q_body(const D3Params& p, char* smem, const in
             for (int j = 0; j < PBW; ++j) {
                 const int m = mBase + 16 * j;
                 float v[8];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    v[e] = acc[2 * ip][j][e] * s0[e] + h0[e];
-                    v[4 + e] = acc[2 * ip + 1][j][e] * s1[e] + h1[e];
-                }
+                bn8(v, acc[2 * ip][j], acc[2 * ip + 1][j], s0, s1, h0, h1);
                 clampn<8>(v, act);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float lo, hi;
-                    unpack2<DT>(rr[j][e], lo, hi);
-                    v[2 * e] += lo;
-                    v[2 * e + 1] += hi;
-                }
+                add_skip8<DT>(v, rr[j]);
                 clampn<8>(v, pact);
                 guard.see(v);
                 u32x4 o;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) o[e] = pack2<DT>(v[2 * e], v[2 * e + 1]);
                 const bool ok = chok && m < p.M && !D3_DBG(1);
-                const uint32_t boff = ok ? (uint32_t)(((size_t)m * p.Ypitch + ch0) * 2) : 0x80000000u;
+                const uint32_t boff = ok ? nhwc_off((size_t)m, p.Ypitch, ch0) : kOutOfRange;
                 __builtin_amdgcn_raw_buffer_store_b128(o, yrsrc, boff, 0, 0);
             }
         }

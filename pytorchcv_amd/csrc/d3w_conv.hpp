@@ -30,10 +30,7 @@
 //   * Epilogue of a tile: both groups in the SAME interval (group 0 in front of its first reads of the next tile, group 1 behind
 //     its last MFMAs), with the first two K-steps of the next tile already in the ring.
 #pragma once
-#include <type_traits>
-#include "pcv_common.hpp"
-#include "igemm_conv.hpp"     // Mma<DT>, FastDiv
-#include "d3q_conv.hpp"       // D3Params, D3Tiles, d3q_tiles, d3q_sync
+#include "conv_device.hpp"
 
 // WC x WP: wave grid (channels x pixels), 8 waves. CBW / PBW: 16-row blocks per wave (channels / pixels).
 // NSA_: slots of the weight ring (3: the tile of K-step s + 2 is issued during K-step s; 2: the tile of s + 1, due at the end of s - for
@@ -100,11 +97,10 @@ __device__ __forceinline__ void d3w_body(const D3Params& p, char* smem, const in
     uint64_t rt1__ = 0, rt2__ = 0, cy1__ = 0, cy2__ = 0;
 #endif
 
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w), 0, p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrsrc = buffer_rsrc(p.w, p.w_bytes);
     // activations: descriptor base one image row BELOW x (d3q_conv.hpp: the scalar offset of a group reaches the row above with r = 0)
     const uint32_t rowBytes = (uint32_t)(p.W * p.Cin * 2);
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char*>(reinterpret_cast<const char*>(p.x)) - rowBytes, 0, p.x_bytes + 2u * rowBytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrsrc = buffer_rsrc(reinterpret_cast<const char*>(p.x) - rowBytes, p.x_bytes + 2u * rowBytes);
 
     // ---- DMA side: this wave owns weight pieces 8 i + wave (rows 8 (8 i + wave) + lrow) and activation pieces 8 j + wave ----
     // The cursor runs two K-steps (weights) / one group (activations) ahead of the compute side: K-step s issues K-step s + 2.
@@ -272,13 +268,13 @@ __device__ __forceinline__ void d3w_body(const D3Params& p, char* smem, const in
             *reinterpret_cast<__attribute__((address_space(3))) float*>((size_t)(lds0 + G::SSOFF + 4 * i)) = v;
         }
     };
-    // Epilogue (d3q_conv.hpp): v = acc * scale + shift -> act -> (+ residual) -> post_act -> one 16-byte NHWC store per (channel pair,
+    // Epilogue (d3q_conv.hpp; the steps: conv_device.hpp): v = acc * scale + shift -> act -> (+ residual) -> post_act -> one 16-byte NHWC store per (channel pair,
     // pixel block); branch-free, activations none / ReLU / ReLU6. Residual tiles are fetched four pixel blocks at a time.
     auto epilogue = [&](int t, auto HRc) __attribute__((always_inline)) {
         constexpr bool HR = decltype(HRc)::value;
         const ActClamp act = make_act(p.act), pact = make_act(p.post_act);
-        const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.res), 0, HR ? p.res_bytes : 0u, 0x00020000);
+        const __amdgpu_buffer_rsrc_t yrsrc = buffer_rsrc(p.y, p.y_bytes);
+        const __amdgpu_buffer_rsrc_t rrsrc = buffer_rsrc(p.res, HR ? p.res_bytes : 0u);
         const int chTile = t % p.nChTiles;
         const int tileP0 = (t / p.nChTiles) * BP;
         const int mBase = tileP0 + wp * 16 * PBW + fr;
@@ -301,7 +297,7 @@ __device__ __forceinline__ void d3w_body(const D3Params& p, char* smem, const in
                         const int j = j0 + jj;
                         if (j < PBW) {
                             const int m = mBase + 16 * j;
-                            const uint32_t roff = (chok && m < p.M && (TRIM == 0 || m - tileP0 < BP)) ? (uint32_t)(((size_t)m * p.Cout + ch0) * 2) : 0x80000000u;
+                            const uint32_t roff = (chok && m < p.M && (TRIM == 0 || m - tileP0 < BP)) ? nhwc_off((size_t)m, p.Cout, ch0) : kOutOfRange;
                             rr[jj] = __builtin_amdgcn_raw_buffer_load_b128(rrsrc, roff, 0, 0);
                         }
                     }
@@ -312,28 +308,16 @@ __device__ __forceinline__ void d3w_body(const D3Params& p, char* smem, const in
                     if (j < PBW) {
                         const int m = mBase + 16 * j;
                         float v[8];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            v[e] = acc[2 * ip][j][e] * s0[e] + h0[e];
-                            v[4 + e] = acc[2 * ip + 1][j][e] * s1[e] + h1[e];
-                        }
+                        bn8(v, acc[2 * ip][j], acc[2 * ip + 1][j], s0, s1, h0, h1);
                         clampn<8>(v, act);
-                        if constexpr (HR) {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                float lo, hi;
-                                unpack2<DT>(rr[jj][e], lo, hi);
-                                v[2 * e] += lo;
-                                v[2 * e + 1] += hi;
-                            }
-                        }
+                        if constexpr (HR) add_skip8<DT>(v, rr[jj]);
                         clampn<8>(v, pact);
                         if (TRIM == 0 || wp * PBW + j < PBW * WP - TRIM) guard.see(v);      // (a block past a trimmed tile's end holds garbage)
                         u32x4 o;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) o[e] = pack2<DT>(v[2 * e], v[2 * e + 1]);
                         const bool ok = chok && m < p.M && (TRIM == 0 || m - tileP0 < BP);      // (trimmed tiles: the blocks past the tile's end)
-                        const uint32_t boff = ok ? (uint32_t)(((size_t)m * p.Ypitch + ch0) * 2) : 0x80000000u;
+                        const uint32_t boff = ok ? nhwc_off((size_t)m, p.Ypitch, ch0) : kOutOfRange;
                         __builtin_amdgcn_raw_buffer_store_b128(o, yrsrc, boff, 0, 0);
                     }
                 }

@@ -135,13 +135,6 @@ __device__ __forceinline__ f32x2 pk_mul(const f32x2& a, const f32x2& b) {
     return r;
 }
 
-template <int... I, typename F> __device__ __forceinline__ void static_for_impl(std::integer_sequence<int, I...>, F&& f) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
-    static_for_impl(std::make_integer_sequence<int, N>{}, static_cast<F&&>(f));
-}
-
 // FAST: both activations are none/relu/relu6 (a clamp); the general activation codes live in the FAST=false build so
 // that their transcendental code does not bloat the hot kernel.
 // CPT: channels per thread (8, or 4 for the 5x5 window whose 25 taps x 8 channels would not fit the register file).
@@ -166,7 +159,7 @@ __global__ __launch_bounds__(256, 2) void dwconv_kernel(const DwParams p) {
     const int ho_begin = seg * p.TH;
     const int ho_end = min(p.Ho, ho_begin + p.TH);
 
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.x), 0, p.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrsrc = buffer_rsrc(p.x, p.x_bytes);
 
     constexpr int NV = CPT / 2;          // packed fp32 pairs per chunk
     f32x2 wgt[KS * KS][NV];
@@ -317,7 +310,7 @@ __global__ __launch_bounds__(256, 2) void dwconv5_kernel(const DwParams p) {
     const int ho_begin = seg * p.TH;
     const int nrows = min(p.Ho, ho_begin + p.TH) - ho_begin;
 
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.x), 0, p.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrsrc = buffer_rsrc(p.x, p.x_bytes);
 
     f32x2 wgt[KS * KS][NV];
 #pragma unroll

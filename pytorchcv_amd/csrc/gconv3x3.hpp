@@ -16,7 +16,6 @@
 // HBM-bound by construction: one 128-byte read and one write per pixel and 64 channels (+ halo rows, L2 hits).
 #pragma once
 #include "pcv_common.hpp"
-#include "igemm_conv.hpp"     // Mma<DT>, FastDiv
 
 struct GConvParams {
     const void* x;
@@ -31,10 +30,6 @@ struct GConvParams {
     int act;
     uint32_t* ovf;          // the context's fp16 overflow counter (pcv_common.hpp, F16Guard)
 };
-
-template <int N> __device__ __forceinline__ void gconv_wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 template <int WPAD> struct GConvCfg {
     static constexpr int BP = 128, XR = BP + 2 * WPAD, XL = XR / 32;       // tile rows, LDS-DMA pieces per thread
@@ -65,9 +60,9 @@ __global__ __launch_bounds__(256, 2) void gconv3x3_kernel(const GConvParams p) {
     const int tend = min(p.nTiles, (xcd + 1) * perXcd);
     if (tile >= tend) return;
 
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.x), 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w), 0, p.w_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrsrc = buffer_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t wrsrc = buffer_rsrc(p.w, p.w_bytes);
+    const __amdgpu_buffer_rsrc_t yrsrc = buffer_rsrc(p.y, p.y_bytes);
 
     // tile t = (channel block t / nPixTiles, pixel tile t % nPixTiles): a block mostly stays inside one channel block
     auto issue_x = [&](int t, int xb, bool live) {
@@ -126,8 +121,8 @@ __global__ __launch_bounds__(256, 2) void gconv3x3_kernel(const GConvParams p) {
             m_hi |= ((int)w == p.W - 1 ? 1u : 0u) << j;
         }
         // X(tile) landed: the only younger VMEM ops of this wave are the previous tile's 8 stores (a weight reload waits for all)
-        if (reloaded) gconv_wait_vmcnt<0>();
-        else gconv_wait_vmcnt<4 * PBW>();
+        if (reloaded) wait_vmcnt<0>();
+        else wait_vmcnt<4 * PBW>();
         __builtin_amdgcn_s_barrier();                  // ... for every wave; the other buffer is no longer read
         asm volatile("" ::: "memory");
         issue_x(ntile, xb ^ 1, has_next);
@@ -184,7 +179,7 @@ __global__ __launch_bounds__(256, 2) void gconv3x3_kernel(const GConvParams p) {
         tile = ntile;
         xb ^= 1;
     }
-    gconv_wait_vmcnt<0>();                             // the look-ahead DMA of the last tile (issued out of range)
+    wait_vmcnt<0>();                             // the look-ahead DMA of the last tile (issued out of range)
 #endif  // __HIP_DEVICE_COMPILE__
 }
 

@@ -15,7 +15,7 @@
 //   * all weights of the 64-channel block stay in registers while consecutive tiles keep the channel block.
 // HBM-bound by construction: every input pixel's 128-byte segment is read once per tile (+ 1 halo row in 2 R + 1, L2 / MALL hits).
 #pragma once
-#include "gconv3x3.hpp"
+#include "gconv3x3.hpp"       // the companion kernel: GConvParams, GConvCfg and its weight blob (KT = 5) are used as they are
 
 struct GConvRParams {
     const void* x;
@@ -58,9 +58,9 @@ __global__ __launch_bounds__(256, 2) void gconv3x3r_kernel(const GConvRParams p)
     const int tend = min(p.nTiles, (xcd + 1) * perXcd);
     if (tile >= tend) return;
 
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.x), 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w), 0, p.w_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrsrc = buffer_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t wrsrc = buffer_rsrc(p.w, p.w_bytes);
+    const __amdgpu_buffer_rsrc_t yrsrc = buffer_rsrc(p.y, p.y_bytes);
     const int xbuf = p.xl * (32 * 128);
 
     // tile t = (channel block t / nRowTiles, output rows R (t % nRowTiles) .. + R); window pixel c' = c - cbase lives in LDS row
@@ -124,8 +124,8 @@ __global__ __launch_bounds__(256, 2) void gconv3x3r_kernel(const GConvRParams p)
         const bool at_top = gh == 0;
         const bool at_bot = S == 1 && gh == p.Ho - 1;  // stride 2, even H: row 2 ho + 1 is always inside
         // X(tile) landed: the only younger VMEM ops of this wave are the previous tile's 4 stores (a weight reload waits for all)
-        if (reloaded) gconv_wait_vmcnt<0>();
-        else gconv_wait_vmcnt<4>();
+        if (reloaded) wait_vmcnt<0>();
+        else wait_vmcnt<4>();
         __builtin_amdgcn_s_barrier();                  // ... for every wave; the other buffer is no longer read
         asm volatile("" ::: "memory");
         issue_x(ntile, xb ^ 1, has_next);
@@ -189,7 +189,7 @@ __global__ __launch_bounds__(256, 2) void gconv3x3r_kernel(const GConvRParams p)
         tile = ntile;
         xb ^= 1;
     }
-    gconv_wait_vmcnt<0>();                             // the look-ahead DMA of the last tile (issued out of range)
+    wait_vmcnt<0>();                             // the look-ahead DMA of the last tile (issued out of range)
 #endif  // __HIP_DEVICE_COMPILE__
 }
 

@@ -66,32 +66,6 @@ struct IgemmParams {
     uint32_t* ovf;          // the context's fp16 overflow counter (pcv_common.hpp, F16Guard)
 };
 
-template <int DT> struct Mma;
-template <> struct Mma<PCV_BF16> {
-    typedef s16x8 frag;
-    static __device__ __forceinline__ f32x4 run(const frag& a, const frag& b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-    }
-};
-template <> struct Mma<PCV_F16> {
-    typedef f16x8 frag;
-    static __device__ __forceinline__ f32x4 run(const frag& a, const frag& b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-    }
-};
-template <> struct Mma<PCV_F32> {
-    // exact-f32 MFMA (v_mfma_f32_16x16x4_f32): the 16-byte chunk held by lane group q carries k = 4q+e, and
-    // MFMA e (0..3) sums element e over the four lane groups - the same k association on both operands.
-    typedef f32x4 frag;
-    static __device__ __forceinline__ f32x4 run(const frag& a, const frag& b, f32x4 c) {
-        c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b[0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b[1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b[2], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b[3], c, 0, 0, 0);
-        return c;
-    }
-};
-
 // DT: storage type of x / w / residual.  OT: storage type of y.  CB: 16-channel blocks per wave (2 or 4).
 // PB: 16-pixel blocks per wave.  WC x WP: wave grid (channels x pixels).  RAGGED: Cout not a multiple of 8.
 // KHW: 0 = taps from the descriptor table, 1 = 1x1 without padding (every tap valid, chunk offsets computed),
@@ -181,10 +155,10 @@ __global__ __launch_bounds__(64 * WC * WP, 2) void igemm_conv_kernel(const Igemm
         }
     };
 
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.x), 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w), 0, p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrsrc = buffer_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t wrsrc = buffer_rsrc(p.w, p.w_bytes);
 
-    const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t yrsrc = buffer_rsrc(p.y, p.y_bytes);
 
     // 16-bit non-ragged outputs are written with range-checked buffer stores: one store instruction per (ip, j) for every
     // wave, no branches in the epilogue (tile tails / channel padding get an offset beyond num_records and are dropped).

@@ -24,7 +24,6 @@
 // next tile's x, which therefore hides completely.
 #pragma once
 #include "pcv_common.hpp"
-#include "igemm_conv.hpp"     // Mma<DT>
 
 struct MbParams {
     const void* x;            // [N,H,W,Cin]
@@ -102,14 +101,14 @@ __global__ __launch_bounds__(256, 2) void mbconv_kernel(const MbParams p) {
     int tile = blockIdx.x;
     if (tile >= p.nTiles) return;
 
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.x), 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.res), 0, p.res ? p.y_bytes : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wersrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w_exp), 0, p.wexp_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wdrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w_dw), 0, p.wdw_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wprsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w_proj), 0, p.wproj_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t sprsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.scale_p), 0, p.Cout * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t hprsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.shift_p), 0, p.Cout * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrsrc = buffer_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t yrsrc = buffer_rsrc(p.y, p.y_bytes);
+    const __amdgpu_buffer_rsrc_t rrsrc = buffer_rsrc(p.res, p.res ? p.y_bytes : 0);
+    const __amdgpu_buffer_rsrc_t wersrc = buffer_rsrc(p.w_exp, p.wexp_bytes);
+    const __amdgpu_buffer_rsrc_t wdrsrc = buffer_rsrc(p.w_dw, p.wdw_bytes);
+    const __amdgpu_buffer_rsrc_t wprsrc = buffer_rsrc(p.w_proj, p.wproj_bytes);
+    const __amdgpu_buffer_rsrc_t sprsrc = buffer_rsrc(const_cast<float*>(p.scale_p), p.Cout * 4);
+    const __amdgpu_buffer_rsrc_t hprsrc = buffer_rsrc(const_cast<float*>(p.shift_p), p.Cout * 4);
 
     // ---- the unit's weights -> LDS, once per block -------------------------------------------------------------------------
     // slabs of 16 rows x 64 B per LDS-DMA instruction; lane L -> row 16*piece + (L >> 2), physical slot L & 3, which must

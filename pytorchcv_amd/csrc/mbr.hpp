@@ -32,7 +32,6 @@
 #pragma once
 #include <type_traits>
 #include "pcv_common.hpp"
-#include "igemm_conv.hpp"     // Mma<DT>
 #include "mbconv.hpp"         // MbParams
 #include "mbw.hpp"            // mbw_swz, mbw_act
 
@@ -156,9 +155,9 @@ __global__ __launch_bounds__(64 * WAVES) void mbr_kernel(const MbParams p) {
     int ntile__ = 0;
 #endif
 
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.x), 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.res), 0, p.res ? p.y_bytes : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrsrc = buffer_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t yrsrc = buffer_rsrc(p.y, p.y_bytes);
+    const __amdgpu_buffer_rsrc_t rrsrc = buffer_rsrc(p.res, p.res ? p.y_bytes : 0);
 
     // ---- the unit's weights and BN constants -> LDS, once per block -------------------------------------------------------------------
     // ONE loop over every 16-byte piece of the five tables, four independent loads in flight per thread: as five loops of
@@ -229,8 +228,8 @@ __global__ __launch_bounds__(64 * WAVES) void mbr_kernel(const MbParams p) {
     const char* const we_rd = Wes + fr * 64 + fsw;
     const char* const wp_rd = Wps + fr * 64 + fsw;
     const char* const af_rd = Afs + lane * 16;
-    const __amdgpu_buffer_rsrc_t wersrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w_exp), 0, p.wexp_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t afrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w_dwsp), 0, (uint32_t)(p.nChunks * 6 * 1024), 0x00020000);
+    const __amdgpu_buffer_rsrc_t wersrc = buffer_rsrc(p.w_exp, p.wexp_bytes);
+    const __amdgpu_buffer_rsrc_t afrsrc = buffer_rsrc(p.w_dwsp, (uint32_t)(p.nChunks * 6 * 1024));
     // sparse index of this lane's A rows (MmaSp): every group keeps positions (i % 4, 3) - the weight in the pair's first slot, a zero in
     // the second - or (0, 3) with the weight second for i % 4 == 3; all eight 4-bit fields alike
     const int spidx = (((fr & 3) == 3 ? 0 : (fr & 3)) | (3 << 2)) * 0x11111111;

@@ -27,7 +27,6 @@
 // runs are 8 k rows apart; they are kept selectable, the default is 1 x 16.
 #pragma once
 #include "pcv_common.hpp"
-#include "igemm_conv.hpp"     // Mma<DT>
 #include "mbconv.hpp"         // MbParams
 
 struct MbwLds {
@@ -119,14 +118,14 @@ __global__ __launch_bounds__(512) void mbw_kernel(const MbParams p) {
     char* const Ds = Es + NPT * 16 * PITCH;
     const int CmidP = p.nChunks * 32;
 
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.x), 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.res), 0, p.res ? p.y_bytes : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wersrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w_exp), 0, p.wexp_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wdrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w_dw), 0, p.wdw_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wprsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w_proj), 0, p.wproj_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t sprsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.scale_p), 0, p.Cout * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t hprsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.shift_p), 0, p.Cout * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrsrc = buffer_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t yrsrc = buffer_rsrc(p.y, p.y_bytes);
+    const __amdgpu_buffer_rsrc_t rrsrc = buffer_rsrc(p.res, p.res ? p.y_bytes : 0);
+    const __amdgpu_buffer_rsrc_t wersrc = buffer_rsrc(p.w_exp, p.wexp_bytes);
+    const __amdgpu_buffer_rsrc_t wdrsrc = buffer_rsrc(p.w_dw, p.wdw_bytes);
+    const __amdgpu_buffer_rsrc_t wprsrc = buffer_rsrc(p.w_proj, p.wproj_bytes);
+    const __amdgpu_buffer_rsrc_t sprsrc = buffer_rsrc(const_cast<float*>(p.scale_p), p.Cout * 4);
+    const __amdgpu_buffer_rsrc_t hprsrc = buffer_rsrc(const_cast<float*>(p.shift_p), p.Cout * 4);
 
     // ---- the unit's weights -> LDS, once per block (rows beyond the packed matrices / channels beyond Cmid read as zeros) --------
     for (int i = tid; WLDS && i < p.nChunks * 32 * 4; i += blockDim.x) {

@@ -23,10 +23,7 @@
 //   * the partial last round of a persistent grid is split into its 16-pixel units, one per block (`tailN`, below).
 // LDS image of a unit (16 pixels): [64-channel slice][16 rows x 128 B], 16-byte chunk slot s of row R holds K-chunk s ^ (R & 7).
 #pragma once
-#include <type_traits>
-#include "pcv_common.hpp"
-#include "igemm_conv.hpp"     // Mma<DT>
-#include "d3q_conv.hpp"       // D3Params, D3Tiles, d3q_tiles
+#include "conv_device.hpp"
 
 template <int CW_, int CIN_>
 struct P1RCfg {
@@ -79,11 +76,11 @@ __device__ __forceinline__ void p1r_body(const D3Params& p, char* smem) {
     const uint64_t cstart__ = __builtin_amdgcn_s_memtime();
 #endif
 
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w), 0, p.w_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.x), 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrsrc = buffer_rsrc(p.w, p.w_bytes);
+    const __amdgpu_buffer_rsrc_t xrsrc = buffer_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t yrsrc = buffer_rsrc(p.y, p.y_bytes);
     const bool has_res = p.res != nullptr;
-    const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.res), 0, has_res ? p.res_bytes : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rrsrc = buffer_rsrc(p.res, has_res ? p.res_bytes : 0u);
 
     // ---- weights: A fragments of this wave's CW channels, all K-halves (reloaded when the channel group changes) ----
     frag A[KH][CWB];
@@ -148,10 +145,8 @@ __device__ __forceinline__ void p1r_body(const D3Params& p, char* smem) {
         constexpr int u = st / KH, kh = st - KH * u, s = kh >> 1, h = kh & 1;
         bq[st % RING] = *reinterpret_cast<lds_fptr>((size_t)(h ? fs1 : fs0) + (size_t)(u * G::UNITB + s * 2048));
     };
-    // activations as branch-free clamps to launch-uniform bounds (d3c_conv.hpp)
-    const float alo = (p.act == PCV_ACT_RELU || p.act == PCV_ACT_RELU6) ? 0.f : -INFINITY, ahi = p.act == PCV_ACT_RELU6 ? 6.f : INFINITY;
-    const float plo = (p.post_act == PCV_ACT_RELU || p.post_act == PCV_ACT_RELU6) ? 0.f : -INFINITY, phi = p.post_act == PCV_ACT_RELU6 ? 6.f : INFINITY;
-    const float clo = alo > plo ? alo : plo, chi = ahi < phi ? ahi : phi;
+    // activations as branch-free clamps to launch-uniform bounds (conv_device.hpp)
+    const EpiBounds B = make_epi_bounds(p.act, p.post_act);
     constexpr int NRR = G::RES ? TP * (CWB / 2) : 1;              // residual pieces of a tile (32 channels per wave only: 4 / 8)
     u32x4 rrq[NRR];
     u32x4 opend;
@@ -184,18 +179,18 @@ __device__ __forceinline__ void p1r_body(const D3Params& p, char* smem) {
         f32x2 v = (f32x2){c[k0], c[k0 + 1]} * (f32x2){scv[k0], scv[k0 + 1]} + (f32x2){shv[k0], shv[k0 + 1]};      // (contracted: one packed FMA)
         if constexpr (HR) {
             if constexpr (PRE) {
-                v[0] = __builtin_elementwise_maximum(v[0], alo); v[1] = __builtin_elementwise_maximum(v[1], alo);
-                if constexpr (HI) { v[0] = __builtin_elementwise_minimum(v[0], ahi); v[1] = __builtin_elementwise_minimum(v[1], ahi); }
+                v[0] = __builtin_elementwise_maximum(v[0], B.alo); v[1] = __builtin_elementwise_maximum(v[1], B.alo);
+                if constexpr (HI) { v[0] = __builtin_elementwise_minimum(v[0], B.ahi); v[1] = __builtin_elementwise_minimum(v[1], B.ahi); }
             }
             float lo, hi;
             unpack2<DT>(rrq[(u * (CWB / 2) + ip) % NRR][e], lo, hi);
             v += (f32x2){lo, hi};
-            v[0] = __builtin_elementwise_maximum(v[0], plo); v[1] = __builtin_elementwise_maximum(v[1], plo);
-            if constexpr (HI) { v[0] = __builtin_elementwise_minimum(v[0], phi); v[1] = __builtin_elementwise_minimum(v[1], phi); }
+            v[0] = __builtin_elementwise_maximum(v[0], B.plo); v[1] = __builtin_elementwise_maximum(v[1], B.plo);
+            if constexpr (HI) { v[0] = __builtin_elementwise_minimum(v[0], B.phi); v[1] = __builtin_elementwise_minimum(v[1], B.phi); }
         } else {
-            // nothing between the two activations: one clamp to (max(alo, plo), min(ahi, phi)) (d3c_conv.hpp)
-            v[0] = __builtin_elementwise_maximum(v[0], clo); v[1] = __builtin_elementwise_maximum(v[1], clo);
-            if constexpr (HI) { v[0] = __builtin_elementwise_minimum(v[0], chi); v[1] = __builtin_elementwise_minimum(v[1], chi); }
+            // nothing between the two activations: one clamp to (max(B.alo, B.plo), min(B.ahi, B.phi)) (conv_device.hpp)
+            v[0] = __builtin_elementwise_maximum(v[0], B.clo); v[1] = __builtin_elementwise_maximum(v[1], B.clo);
+            if constexpr (HI) { v[0] = __builtin_elementwise_minimum(v[0], B.chi); v[1] = __builtin_elementwise_minimum(v[1], B.chi); }
         }
         guard.see2(v[0], v[1]);
         opend[e] = pack2<DT>(v[0], v[1]);

@@ -26,7 +26,6 @@
 #pragma once
 #include "pcv_common.hpp"
 #include <type_traits>
-#include "igemm_conv.hpp"     // Mma<DT>
 
 struct PairParams {
     const void* x;            // [M][64]
@@ -54,10 +53,6 @@ struct PairParams {
     uint32_t* ovf;            // the context's fp16 overflow counter (pcv_common.hpp, F16Guard)
 };
 
-template <int N> __device__ __forceinline__ void pair_wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 // PB: 16-pixel blocks per tile. PB = 4: 64-pixel tiles, one block per CU (needs > 256 registers); PB = 2: 32-pixel tiles,
 // half the accumulators, fits 256 registers and 44 KB of LDS -> two blocks (8 waves) per CU, which hides HBM latency better.
 template <int DT, int PB, bool IDC = false, bool GATE = false>
@@ -81,14 +76,14 @@ __global__ __launch_bounds__(256, PB == 4 ? 1 : 2) void pair1x1_kernel(const Pai
     const int tstride = gridDim.x;
     if (tile >= p.nTiles) return;
 
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.x), 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.res), 0, p.res_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t y1rsrc = __builtin_amdgcn_make_buffer_rsrc(p.y1, 0, p.y1_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t y2rsrc = __builtin_amdgcn_make_buffer_rsrc(p.y2, 0, p.y2_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t w1rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w1), 0, p.w1_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t w2rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w2), 0, p.w2_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t x0rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(IDC ? p.x0 : p.x), 0, IDC ? p.x0_bytes : p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t widrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(IDC ? p.wid : p.w1), 0, IDC ? p.wid_bytes : p.w1_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrsrc = buffer_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t rrsrc = buffer_rsrc(p.res, p.res_bytes);
+    const __amdgpu_buffer_rsrc_t y1rsrc = buffer_rsrc(p.y1, p.y1_bytes);
+    const __amdgpu_buffer_rsrc_t y2rsrc = buffer_rsrc(p.y2, p.y2_bytes);
+    const __amdgpu_buffer_rsrc_t w1rsrc = buffer_rsrc(p.w1, p.w1_bytes);
+    const __amdgpu_buffer_rsrc_t w2rsrc = buffer_rsrc(p.w2, p.w2_bytes);
+    const __amdgpu_buffer_rsrc_t x0rsrc = buffer_rsrc(IDC ? p.x0 : p.x, IDC ? p.x0_bytes : p.x_bytes);
+    const __amdgpu_buffer_rsrc_t widrsrc = buffer_rsrc(IDC ? p.wid : p.w1, IDC ? p.wid_bytes : p.w1_bytes);
 
     // ---- weights -> registers (once) -----------------------------------------------------------------------------
     frag a1[4][2];      // W1 rows 64w + 16i + fr, K-step ks
@@ -196,7 +191,7 @@ __global__ __launch_bounds__(256, PB == 4 ? 1 : 2) void pair1x1_kernel(const Pai
     issue_x(tile + tstride, 1);
     load_res(tile, resr[0]);
     load_res(tile + tstride, resr[1]);
-    pair_wait_vmcnt<0>();
+    wait_vmcnt<0>();
     bool first = true;
 
     F16Guard<DT> guard;
@@ -207,7 +202,7 @@ __global__ __launch_bounds__(256, PB == 4 ? 1 : 2) void pair1x1_kernel(const Pai
         // x(t) landed: all but the 5 PB youngest VMEM ops of this wave are done - those are the previous iteration's
         // x(t+2) [PB/2], residual(t+2) [2 PB], y1 stores [2 PB], y2 stores [PB/2] (always issued, out of range when invalid).
         // IDC: x(t+2) + x0(t+2) [PB], no residual loads, y1 stores [2 PB], y2 stores [PB/2].
-        if (!first) pair_wait_vmcnt<IDC ? (7 * PB) / 2 : 5 * PB>();
+        if (!first) wait_vmcnt<IDC ? (7 * PB) / 2 : 5 * PB>();
         first = false;
         __syncthreads();
 

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
+#include <utility>
 #include "../../include/pcv_amd.h"
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -13,6 +15,63 @@ typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
 
 #define PCV_LDS(p) ((__attribute__((address_space(3))) void*)(p))
+
+// ---- small device helpers ------------------------------------------------------------------------------
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>), in order: a loop whose index is a compile-time constant in
+// every iteration (register-array indices, `if constexpr` per step)
+template <typename F, int... I> __device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
+    (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
+    static_for_impl(static_cast<F&&>(f), std::make_integer_sequence<int, N>{});
+}
+// at most N of this wave's vector-memory operations (LDS-DMA pieces included) are still in flight; opaque to the compiler's own
+// wait-count pass (where that pass must see the wait, a kernel uses __builtin_amdgcn_s_waitcnt)
+template <int N> __device__ __forceinline__ void wait_vmcnt() {
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+// A byte offset no buffer descriptor here covers (the host keeps every tensor below 2 GiB): a load at it returns zeros, a store is
+// dropped - the range check stands in for a branch.
+constexpr uint32_t kOutOfRange = 0x80000000u;
+// byte offset of channel ch0 of row m in a 16-bit NHWC tensor of `pitch` channels per pixel. The arithmetic runs in m's type: int
+// where the host bounds the tensor by 2 GiB, size_t where the kernel does not rely on that. A guarded offset is written
+// `ok ? nhwc_off(m, pitch, ch0) : kOutOfRange` where `ok` is tested (as a bool argument the condition compiles differently).
+template <typename I> __device__ __forceinline__ uint32_t nhwc_off(I m, int pitch, int ch0) {
+    return (uint32_t)((m * pitch + ch0) * 2);
+}
+#if defined(__HIP_DEVICE_COMPILE__)      // (buffer-resource types are device-only)
+// raw buffer descriptor over `bytes` bytes at p (num_records = bytes: every access is range-checked against it)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buffer_rsrc(const void* p, uint32_t bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
+}
+#endif
+
+// ---- one MFMA K-half (16 x 16 output block, 32 elements of K; fp32 storage: 16) per storage type -------------
+template <int DT> struct Mma;
+template <> struct Mma<PCV_BF16> {
+    typedef s16x8 frag;
+    static __device__ __forceinline__ f32x4 run(const frag& a, const frag& b, f32x4 c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+    }
+};
+template <> struct Mma<PCV_F16> {
+    typedef f16x8 frag;
+    static __device__ __forceinline__ f32x4 run(const frag& a, const frag& b, f32x4 c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+    }
+};
+template <> struct Mma<PCV_F32> {
+    // exact-f32 MFMA (v_mfma_f32_16x16x4_f32): the 16-byte chunk held by lane group q carries k = 4q+e, and
+    // MFMA e (0..3) sums element e over the four lane groups - the same k association on both operands.
+    typedef f32x4 frag;
+    static __device__ __forceinline__ f32x4 run(const frag& a, const frag& b, f32x4 c) {
+        c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b[0], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b[1], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b[2], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b[3], c, 0, 0, 0);
+        return c;
+    }
+};
 
 // ---- element traits: storage type tag -> bytes, conversions -------------------------------------------
 template <int DT> struct Elem;

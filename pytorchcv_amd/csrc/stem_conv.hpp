@@ -26,7 +26,6 @@
 #pragma once
 #include <type_traits>
 #include "pcv_common.hpp"
-#include "igemm_conv.hpp"     // Mma<DT>
 
 struct StemParams {
     const void* x;            // NHWC4 [N, H, Wp, 4], Wp even, pad column/channel zero
@@ -91,9 +90,9 @@ __global__ __launch_bounds__(256, 2) void stem_conv_kernel(const StemParams p) {
     const int tend = min(p.nTiles, (xcd + 1) * perXcd);
     if (tile >= tend) return;
 
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.x), 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w), 0, p.w_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrsrc = buffer_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t wrsrc = buffer_rsrc(p.w, p.w_bytes);
+    const __amdgpu_buffer_rsrc_t yrsrc = buffer_rsrc(p.y, p.y_bytes);
 
     // ---- weights: loaded once. LDS row (r, ch) is 64 B = 4 chunks; chunk slot s holds K-chunk s ^ f(ch) with
     //      f = [0,2,3,1][(ch >> 2) & 3], which makes the 16-lane ds_read_b128 groups conflict-free on 64-byte rows.

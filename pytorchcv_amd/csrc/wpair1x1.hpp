@@ -28,7 +28,6 @@
 //   a DMA issued only half a chunk earlier, 109 us against 102 us unfused; a wave owning 16 pixels alone did no better.)
 #pragma once
 #include "pcv_common.hpp"
-#include "igemm_conv.hpp"     // Mma<DT>
 
 struct WPairParams {
     const void* x;            // [M][CM]
@@ -51,10 +50,6 @@ struct WPairParams {
     uint32_t hw;
     uint32_t* ovf;            // the context's fp16 overflow counter (pcv_common.hpp, F16Guard)
 };
-
-template <int N> __device__ __forceinline__ void wpair_wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 template <int CM, int C1_ = 4 * CM> struct WPairCfg {
     static constexpr int C1 = C1_;                      // 4 CM in ResNet, 2 CM in ResNeXt 32x4d (resnext.py:62-80)
@@ -113,12 +108,12 @@ __global__ __launch_bounds__((64 * WPairCfg<CM, C1_>::NW), 2) void wpair1x1_kern
     const int tstride = gridDim.x;
     if (tile >= p.nTiles) return;
 
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.x), 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.res), 0, p.res_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t y1rsrc = __builtin_amdgcn_make_buffer_rsrc(p.y1, 0, p.y1_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t y2rsrc = __builtin_amdgcn_make_buffer_rsrc(p.y2, 0, p.y2_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t w1rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w1), 0, p.w1_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t w2rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w2), 0, p.w2_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrsrc = buffer_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t rrsrc = buffer_rsrc(p.res, p.res_bytes);
+    const __amdgpu_buffer_rsrc_t y1rsrc = buffer_rsrc(p.y1, p.y1_bytes);
+    const __amdgpu_buffer_rsrc_t y2rsrc = buffer_rsrc(p.y2, p.y2_bytes);
+    const __amdgpu_buffer_rsrc_t w1rsrc = buffer_rsrc(p.w1, p.w1_bytes);
+    const __amdgpu_buffer_rsrc_t w2rsrc = buffer_rsrc(p.w2, p.w2_bytes);
 
     // ---- BN tables -> LDS (once per persistent block) ---------------------------------------------------------------
     for (int i = tid; i < C1; i += NT) { tsc1[i] = p.scale1[i]; tsf1[i] = p.shift1[i]; }
@@ -222,9 +217,9 @@ __global__ __launch_bounds__((64 * WPairCfg<CM, C1_>::NW), 2) void wpair1x1_kern
             // DMA(c) of this wave landed: younger VMEM ops are the residual prefetch of chunk c and the y1 stores of
             // chunk c-1; at a tile start also the y2 stores and the x loads: wait for everything there.
             if (c == 0) {
-                wpair_wait_vmcnt<0>();
+                wait_vmcnt<0>();
                 if constexpr (GATE && G::GATE_LDS) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the gate rows are written
-            } else wpair_wait_vmcnt<YOUNG>();
+            } else wait_vmcnt<YOUNG>();
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
             // next chunk's weights into the slot every wave has finished reading (chunk c-1)
@@ -373,6 +368,6 @@ __global__ __launch_bounds__((64 * WPairCfg<CM, C1_>::NW), 2) void wpair1x1_kern
         load_x(tile, xf);
     }
     // one weight request is still in flight (made by the last chunk of the last tile): drain before the LDS is released
-    wpair_wait_vmcnt<0>();
+    wait_vmcnt<0>();
 #endif  // __HIP_DEVICE_COMPILE__
 }

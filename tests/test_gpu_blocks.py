@@ -719,6 +719,10 @@ _RW_KERNELS = {  # kernel -> (ConvBlock factory name, input channels, H, W, tuni
     "p1r": ("conv1x1_block", 512, 14, 14, "p1r", {"d1x1": 0}),
     "d1i": ("conv1x1_block", 1024, 14, 14, "d1i", {"d1x1": 0, "d1i": 0}),
     "p1r256": ("conv1x1_block", 256, 14, 14, "p1r", {"d1x1": 0}),
+    # the 8-wave kernels and d3q's 1x1 mode, which every other test runs with ReLU only: the smallest shapes they accept
+    "d3q": ("conv3x3_block", 64, 10, 14, "d3x3", {"d3x3": 0}),
+    "d3w": ("conv3x3_block", 64, 10, 14, "d3w", {"d3x3": 0}),
+    "d1q": ("conv1x1_block", 192, 9, 11, "d1x1", {"d1x1": 0}),
 }
 
 
@@ -726,8 +730,8 @@ _RW_KERNELS = {  # kernel -> (ConvBlock factory name, input channels, H, W, tuni
 @pytest.mark.parametrize("variant", ["none+res", "relu6", "relu6+res+relu6", "none+res+relu", "concat", "concat+res"])
 @pytest.mark.parametrize("kernel", sorted(_RW_KERNELS))
 def test_register_weight_kernels_epilogue_variants_equal_generic(kernel, variant, dtype, cuda_device):
-    """The epilogue forms of the register-weight kernels (d3c / d3k / p1r) that the ReLU-only shape sweeps above never run on their own
-    (ADVICE r4): no activation + skip tensor (the real bottleneck conv3 form, p1r MODE 1), the ReLU6 upper clamps (ahi / phi, p1r MODE 4),
+    """The epilogue forms of the register-weight kernels (d3c / d3k / p1r) and of the 8-wave kernels (d3q / d3w / d3q's 1x1 mode) that
+    the ReLU-only shape sweeps above never run on their own: no activation + skip tensor (the real bottleneck conv3 form, p1r MODE 1), the ReLU6 upper clamps (ahi / phi, p1r MODE 4),
     activation in front of AND behind the skip add, and stores into a channel slice of a wider tensor (y_cpitch > Cout: `out=`) -
     each bit for bit against the generic implicit-GEMM kernel."""
     import pytorchcv_amd

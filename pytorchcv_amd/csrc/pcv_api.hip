@@ -366,8 +366,11 @@ static const char* plan_conv(const pcv_conv_desc& d, ConvPlan& P, bool tables) {
         P.w_bytes = (size_t)d.kh * 64 * 32 * P.ES;
         P.total_bytes = P.w_bytes;
     }
-    P.Ho = (d.H + d.pad_t + d.pad_b - d.dil_h * (d.kh - 1) - 1) / d.stride_h + 1;
-    P.Wo = (d.W + d.pad_l + d.pad_r - d.dil_w * (d.kw - 1) - 1) / d.stride_w + 1;
+    // (a dilated filter larger than the padded input has no output: C's division rounds a negative extent towards zero, which at
+    // stride >= 2 would make one output row / column out of nothing)
+    const int eh = d.H + d.pad_t + d.pad_b - d.dil_h * (d.kh - 1) - 1, ew = d.W + d.pad_l + d.pad_r - d.dil_w * (d.kw - 1) - 1;
+    P.Ho = eh < 0 ? 0 : eh / d.stride_h + 1;
+    P.Wo = ew < 0 ? 0 : ew / d.stride_w + 1;
 
     if (tables) {
         P.ktab.assign((size_t)P.nk * 8 * 2, 0);
@@ -1830,6 +1833,7 @@ int pcv_gemm_bias(pcv_ctx* ctx, const void* x, const void* packed, const float* 
     PCV_ENTER(ctx);
     pcv_conv_desc d;
     std::memset(&d, 0, sizeof(d));
+    d.struct_size = (int32_t)sizeof(d);
     d.N = N; d.H = 1; d.W = 1; d.Cin = Cin; d.Cout = Cout; d.kh = 1; d.kw = 1;
     d.stride_h = d.stride_w = 1; d.dil_h = d.dil_w = 1; d.groups = 1;
     d.act = PCV_ACT_NONE; d.post_act = PCV_ACT_NONE; d.has_residual = 0;

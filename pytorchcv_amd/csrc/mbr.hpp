@@ -546,8 +546,8 @@ __global__ __launch_bounds__(64 * WAVES) void mbr_kernel(const MbParams p) {
                         v[2 * e] += r0;
                         v[2 * e + 1] += r1;
                     }
-                    if constexpr (!decltype(plain)::value) apply_act8(v, post);
                 }
+                if constexpr (!decltype(plain)::value) apply_act8(v, post);          // post_act also without a skip tensor, as the separate launches
 
                 if constexpr ((MBR_DBG & 512) == 0) { if (ok) guard.see(v); }         // (halo lanes hold garbage that is never stored)
                 u32x4 o;

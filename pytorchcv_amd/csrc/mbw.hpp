@@ -435,8 +435,8 @@ __global__ __launch_bounds__(512) void mbw_kernel(const MbParams p) {
                         v[2 * e] += r0;
                         v[2 * e + 1] += r1;
                     }
-                    apply_act8(v, post);
                 }
+                apply_act8(v, post);                                    // post_act also without a skip tensor, as the separate launches
                 guard.see(v);
                 u32x4 o;
 #pragma unroll

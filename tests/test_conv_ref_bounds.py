@@ -25,7 +25,7 @@ import torch
 import torch.nn.functional as F
 
 from conv_ref import Geom, conv_ref, out_hw, pool_values, round_to
-from test_gpu_conv_sweep import (DTYPES, DTYPES16, F1, F2, F4, F5, FAMILIES, _STEM, base_of, case_id, case_reference, geom_of, plan,
+from test_gpu_conv_sweep import (DTYPES, DTYPES16, F1, F2, F4, F5, F6, F6_GENERIC, F7, F7_GENERIC, F7_R, FAMILIES, _STEM, base_of, case_id, case_reference, geom_of, plan,
                                  x_buffer)
 from test_gpu_dw_se import act64
 
@@ -232,6 +232,28 @@ def test_families_run_where_they_claim():
     for c in F5:
         for dt in DTYPES16:
             assert plan(c, dt).stem, case_id(c)
+    for c in F6 + F6_GENERIC + F7 + F7_GENERIC:
+        assert c.Cin == c.Cout and c.Cin % 64 == 0 and not c.res and c.post == 0 and not c.gate and not c.yslice and not c.tune, case_id(c)
+        for dt in DTYPES16:
+            assert plan(c, dt).gconv and plan(c, dt).ngb > 1, case_id(c)
+        assert not plan(c, "fp32").gconv and plan(c, "fp32").gkernel == "generic"                      # 16 bit only
+    assert all(plan(c, dt).gkernel == "flat" for c in F6 for dt in DTYPES16) and all(plan(c, "bf16").gkernel == "generic" for c in F6_GENERIC)
+    assert {(c.Cin // c.groups, (0 if c.W + 1 <= 16 else (1 if c.W + 1 <= 32 else 2))) for c in F6} == {(g, slot) for g in (4, 8, 16) for slot in (0, 1, 2)}   # gconv_slot
+    assert {c.W for c in F6} == {5, 15, 16, 31, 32, 63} and {c.H for c in F6} == {1, 3, 9} and {c.W for c in F6_GENERIC} == {64}
+    tiles = {(c.N * c.H * c.W + 127) // 128 * (c.Cin // 64) for c in F6}
+    assert 1 in tiles and 9 in tiles and max(tiles) > 16 and any(c.Cin == 128 for c in F6)
+    assert all((c.H * c.W) % 128 != 0 for c in F6 if c.N > 1)                                          # images end inside a 128-pixel tile
+    assert {c.act for c in F6 if (c.N, c.H, c.W, c.groups) == (3, 3, 15, 8)} == set(range(7))
+    assert all(plan(c, dt).gkernel == "rows" for c in F7 for dt in DTYPES16) and all(plan(c, "bf16").gkernel == "generic" for c in F7_GENERIC)
+    assert {(c.sh, c.Cin // c.groups) for c in F7} == {(2, 4), (2, 8), (2, 16), (2, 32), (1, 32)}
+    for s in (1, 2):
+        assert {plan(c, "bf16").R for c in F7 if c.sh == s} == {64, 32, 9, 4, 3, 1}, s
+    for c in F7:
+        P = plan(c, "bf16")
+        assert P.R == F7_R[P.Wo] and (P.R == 1 or c.N * P.Ho % P.R != 0), case_id(c)
+        assert not (c.sh == 2 and (c.H | c.W) & 1)
+    assert all(c.sh == 2 and (c.H | c.W) & 1 for c in F7_GENERIC)
+    assert {c.act for c in F7 if (c.N, c.H, c.W, c.groups) == (2, 10, 14, 4)} == set(range(7)) and any(c.Cin == 128 for c in F7)
     big = [c for c in F1 if (c.N, c.Cin, c.Cout) == (9, 8, 200) and not c.tune][0]
     assert all(9 * 13 * 11 % bp for bp in (64, 128, 256)) and plan(big, "bf16").nPixTiles * plan(big, "bf16").nChTiles > 2 * 8
 
@@ -273,3 +295,6 @@ def test_tuning_defaults_the_sweep_restores_match_the_library():
         m = re.search(r"^\s*int {} = (-?\d+);".format(field), src, re.M)
         assert m and int(m.group(1)) == util._TUNING_DEFAULTS[key], (key, field)
         assert re.search(r'\{{"{}", &pcv_ctx::{}\}}'.format(key, field), src), (key, field)
+    from test_gpu_conv_sweep import K_GCONVR_MAX_LDS
+    m = re.search(r"kGconvRMaxLds = (\d+) \* 1024;", src)
+    assert m and int(m.group(1)) * 1024 == K_GCONVR_MAX_LDS

@@ -1,6 +1,6 @@
 """
 GPU sweep of the two kernels every dedicated dense kernel is compared with bit for bit - the generic implicit GEMM
-(csrc/igemm_conv.hpp) and the stem kernel (csrc/stem_conv.hpp) - against the float64 reference and the derived bound of
+(csrc/igemm_conv.hpp) and the stem kernel (csrc/stem_conv.hpp) - and of the two grouped 3x3 kernels against the float64 reference and the derived bound of
 tests/conv_ref.py (tests/test_conv_ref_bounds.py proves on the CPU that the reference equals torch's float64 convolution, that an
 emulated fp32 kernel stays inside the bound for every case below and that plausible kernel bugs leave it).
 
@@ -14,6 +14,8 @@ dilations. Families:
   F3  the "special" instantiations: ragged Cout, fp32 output from 16-bit input, pcv_gemm_bias
   F4  the pixel-pair scheme on the generic kernel (x_cpitch 4 at 16 bit and not a stem shape)
   F5  the stem kernel: plain, fused max-pool, from fp32 NCHW, both
+  F6  grouped 3x3 on the flat kernel (csrc/gconv3x3.hpp), F7 on the row kernel (csrc/gconv3x3r.hpp) - the only two families that set no
+      switch: the library's own routing, restated in `plan` (route_conv's gconv_ok, plan_gconvr) and asserted first
 Every case runs on the resident grid and under max_blocks = 8 (several tiles per block through the cross-tile pipeline), into a
 NaN-filled output with a guard tail of at least one 256-pixel tile: an element nobody wrote fails the comparison, a write outside
 the tensor (or outside the channel slice of a wider y) fails the guard check. The first assertion of each family restates
@@ -95,7 +97,25 @@ def case_id(c):
 
 
 # ---- plan_conv / route_igemm restated (csrc/pcv_api.hip) ----------------------------------------------------------------------------
-Plan = collections.namedtuple("Plan", "ok pair stem conv3 gconv gpb ngb cin_blk cout_blk special khw nk tile nPixTiles nChTiles Ho Wo")
+Plan = collections.namedtuple("Plan", "ok pair stem conv3 gconv gpb ngb cin_blk cout_blk special khw nk tile nPixTiles nChTiles Ho Wo "
+                              "gkernel R XH wrows")
+K_GCONVR_MAX_LDS = 160 * 1024        # kGconvRMaxLds
+
+
+def plan_gconvr(stride, H, W, Ho, Wo):
+    """plan_gconvr: (R output rows per tile, XH, window rows in LDS), or None where the row-tile kernel does not take the map"""
+    if stride == 2 and ((H | W) & 1):
+        return None
+    if Wo > 64 or Ho <= 0:
+        return None
+    for R in range(64 // Wo, 0, -1):
+        win = (2 * R + 1) * W + 2 if stride == 2 else (R + 2) * W + 2
+        XH = ((win + 1) // 2 + 7) // 8 * 8 if stride == 2 else 0
+        rows = ((2 * XH if stride == 2 else win) + 31) // 32 * 32
+        lds = 2 * rows * 128
+        if lds * 2 <= K_GCONVR_MAX_LDS or (R == 1 and lds <= K_GCONVR_MAX_LDS):
+            return R, XH, rows
+    return None
 
 
 def plan(c, dtype):
@@ -163,8 +183,19 @@ def plan(c, dtype):
         tile = forced
     Ho, Wo = out_hw(c.H, c.W, geom_of(c))
     BM, BP = TILES[tile]
+    # route_conv: the two grouped 3x3 kernels in front of the generic one
+    gconv_ok = (gconv and not c.gate and not c.yslice and not c.res and c.post == NONE and cpitch == c.Cin and c.wpitch in (0, c.W) and
+                c.N * Ho * Wo * c.Cin * 2 < 1 << 31)
+    gkernel, rows = "generic", None
+    if gconv_ok and dict(c.tune).get("gconvr", 1) != 0 and (c.sh == 2 or cgi == 32):
+        rows = plan_gconvr(c.sh, c.H, c.W, Ho, Wo)
+    if rows:
+        gkernel = "rows"
+    elif gconv_ok and c.sh == 1 and cgi != 32 and c.W <= 63:
+        gkernel = "flat"
+    R, XH, wrows = rows or (0, 0, 0)
     return Plan(ok, pair, stem, conv3, gconv, gpb, ngb, cin_blk, cout_blk, special, khw, nk, tile, (c.N * Ho * Wo + BP - 1) // BP,
-                (cout_blk + BM - 1) // BM, Ho, Wo)
+                (cout_blk + BM - 1) // BM, Ho, Wo, gkernel, R, XH, wrows)
 
 
 # ---- F1: table mode, dense ------------------------------------------------------------------------------------------------------------
@@ -271,8 +302,30 @@ _STEM = [
 F5 = [C(N, ci, co, H, W, k=k, s=2, p=p, act=a, cpitch=4, wpitch=W + (W & 1), entry=e, tune=dict(stem32=s32) if co <= 32 else ())
       for (e, k, p, ci, co, (H, W), N, a, s32) in _STEM]
 
+# ---- F6: grouped 3x3 on the flat kernel (csrc/gconv3x3.hpp: 128-pixel tiles, stride 1, 4 / 8 / 16 channels per group, 16 bit) -------------
+# (N, C, groups, H, W): every channels-per-group value in every halo class (W + 1 <= 16 / 32 / 64) and on the classes' edges, H = 1 / 3 / 9,
+# images that end inside a 128-pixel tile, 1 / 9 / more than 16 tiles; C = 128: two channel blocks (the weights are loaded again)
+_F6 = [(1, 64, 16, 1, 5), (3, 64, 8, 3, 15), (5, 64, 4, 9, 16), (4, 64, 16, 9, 31), (3, 64, 8, 3, 32), (4, 64, 4, 9, 63), (2, 64, 8, 1, 63),
+       (7, 64, 4, 3, 5), (3, 64, 16, 9, 15), (9, 64, 16, 1, 16), (2, 64, 4, 9, 32), (2, 64, 16, 3, 32), (2, 64, 8, 9, 16), (3, 128, 8, 9, 31),
+       (5, 128, 16, 9, 31)]
+F6 = ([C(N, ch, ch, H, W, groups=g, act=(RELU, NONE, RELU6)[i % 3]) for i, (N, ch, g, H, W) in enumerate(_F6)] +
+      [C(3, 64, 64, 3, 15, groups=8, act=a) for a in _ACTS])
+F6_GENERIC = [C(2, 64, 64, 3, 64, groups=8, note="W = 64: wider than the flat kernel's halo rows")]
+
+# ---- F7: grouped 3x3 on the row kernel (csrc/gconv3x3r.hpp: R whole output rows per tile; stride 2, and 32 channels per group) ---------------
+# (N, C, groups, H, W, stride): even maps with Wo = 1 / 2 / 7 / 16 / 21 / 64, so that R = 64 / Wo is 64 / 32 / 9 / 4 / 3 / 1; N Ho is no multiple
+# of R (a tile straddles two images) wherever R > 1
+_F7 = [(3, 64, 16, 2, 2, 2), (3, 64, 8, 6, 4, 2), (2, 64, 4, 10, 14, 2), (3, 64, 2, 6, 32, 2), (2, 64, 16, 8, 42, 2), (3, 64, 8, 4, 128, 2),
+       (2, 64, 2, 10, 14, 2), (2, 64, 16, 10, 14, 2), (3, 64, 8, 6, 32, 2), (3, 64, 4, 6, 32, 2), (2, 128, 4, 10, 14, 2),
+       (3, 64, 2, 1, 1, 1), (3, 64, 2, 3, 2, 1), (2, 64, 2, 5, 7, 1), (3, 64, 2, 3, 16, 1), (2, 64, 2, 4, 21, 1), (3, 64, 2, 2, 64, 1),
+       (2, 128, 4, 5, 7, 1)]
+F7_R = {1: 64, 2: 32, 7: 9, 16: 4, 21: 3, 64: 1}            # Wo -> R
+F7 = ([C(N, ch, ch, H, W, s=s, groups=g, act=(RELU, NONE, RELU6)[i % 3]) for i, (N, ch, g, H, W, s) in enumerate(_F7)] +
+      [C(2, 64, 64, 10, 14, s=2, groups=4, act=a) for a in _ACTS])
+F7_GENERIC = [C(2, 64, 64, 15, 15, s=2, groups=16, note="an odd map at stride 2: no parity split")]
+
 FAMILIES = {"F1": (F1, DTYPES), "F2": (F2, DTYPES), "F3": (F3_RAGGED, DTYPES), "F3f": (F3_F32OUT + F3_GEMM, DTYPES16), "F4": (F4, DTYPES16),
-            "F5": (F5, DTYPES16)}
+            "F5": (F5, DTYPES16), "F6": (list(dict.fromkeys(F6)) + F6_GENERIC, DTYPES16), "F7": (list(dict.fromkeys(F7)) + F7_GENERIC, DTYPES16)}
 
 
 def all_cases():
@@ -540,3 +593,23 @@ def test_f5_stem_kernel_vs_float64(c, dtype, cuda_device):
     if c.entry in ("nchw", "nchw_pool"):
         assert c.Cin <= 3 and c.W % 4 == 0 and L.pcv_conv2d_nchw_stem_supported(ctypes.byref(d), int(c.entry == "nchw_pool")) == 1
     sweep("F5", c, dtype, cuda_device, {})
+
+
+# ---- F6 / F7: the grouped 3x3 kernels (no switch is set: the library's own routing) -----------------------------------------------------------
+@pytest.mark.parametrize("c,dtype", _params(FAMILIES["F6"][0], DTYPES16))
+def test_f6_grouped_flat_kernel_vs_float64(c, dtype, cuda_device):
+    P = plan(c, dtype)
+    assert P.ok and P.gconv and c.Cin == c.Cout and c.Cin % 64 == 0 and c.Cin // c.groups in (4, 8, 16), P
+    assert P.gkernel == ("generic" if c.W > 63 else "flat"), P
+    sweep("F6", c, dtype, cuda_device, {})
+
+
+@pytest.mark.parametrize("c,dtype", _params(FAMILIES["F7"][0], DTYPES16))
+def test_f7_grouped_row_kernel_vs_float64(c, dtype, cuda_device):
+    P = plan(c, dtype)
+    assert P.ok and P.gconv and c.Cin == c.Cout and c.Cin % 64 == 0 and (c.sh == 2 or c.Cin // c.groups == 32), P
+    if (c.H | c.W) & 1 and c.sh == 2:
+        assert P.gkernel == "generic", P
+    else:
+        assert P.gkernel == "rows" and P.R == F7_R[P.Wo], P
+    sweep("F7", c, dtype, cuda_device, {})

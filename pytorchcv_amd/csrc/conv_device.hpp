@@ -120,24 +120,7 @@ __device__ __forceinline__ uint32_t epi2(float v0, float v1, uint32_t skip, cons
 //     bn8 -> clampn(act) -> add_skip8 -> clampn(post_act) -> guard.see -> four pack2 -> the 16-byte NHWC store.
 // The steps are helpers, the sequence stays in the kernel: a helper with a branch inside (clampn, a guarded offset, a ternary on a
 // run-time condition) compiles to different code once it is nested in another function, a straight-line one does not
-// (profiles/experiments/kernel_helpers_refactor.md).
-__device__ __forceinline__ void bn8(float (&v)[8], const f32x4& c0, const f32x4& c1, const f32x4& s0, const f32x4& s1, const f32x4& h0,
-                                    const f32x4& h1) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        v[e] = c0[e] * s0[e] + h0[e];
-        v[4 + e] = c1[e] * s1[e] + h1[e];
-    }
-}
-template <int DT> __device__ __forceinline__ void add_skip8(float (&v)[8], const u32x4& skip) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        float lo, hi;
-        unpack2<DT>(skip[e], lo, hi);
-        v[2 * e] += lo;
-        v[2 * e + 1] += hi;
-    }
-}
+// (profiles/experiments/kernel_helpers_refactor.md). bn8 / add_skip8: pcv_common.hpp (the fused-unit kernels use them too).
 // BN scale / shift of channels chl .. chl + 7 (chl: a multiple of 4 inside [0, Cout - 8])
 __device__ __forceinline__ void load_bn8(const D3Params& p, int chl, f32x4& s0, f32x4& s1, f32x4& h0, f32x4& h1) {
     s0 = *reinterpret_cast<const f32x4*>(p.scale + chl); s1 = *reinterpret_cast<const f32x4*>(p.scale + chl + 4);

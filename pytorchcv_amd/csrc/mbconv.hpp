@@ -23,31 +23,7 @@
 // Because the per-chunk operands come from LDS (lgkmcnt), the only vector-memory traffic in flight during a tile is the
 // next tile's x, which therefore hides completely.
 #pragma once
-#include "pcv_common.hpp"
-
-struct MbParams {
-    const void* x;            // [N,H,W,Cin]
-    const void* res;          // [N,Ho,Wo,Cout] or null
-    void* y;                  // [N,Ho,Wo,Cout]
-    const void* w_exp;        // packed rows [round32(Cmid)][Kpad1]        (unused when EXPAND == false)
-    const void* w_dw;         // [9][Cmid]
-    const void* w_dwsp;       // compressed diagonal fragments [chunk][half][filter row][lane] 16 B (pack_dw_sparse_kernel; mbr.hpp)
-    const void* w_proj;       // packed rows [round32(Cout)][Kpad2]
-    const float *scale_e, *shift_e, *scale_d, *shift_d, *scale_p, *shift_p;
-    uint32_t x_bytes, y_bytes, wexp_bytes, wdw_bytes, wproj_bytes;
-    int N, H, W, Cin, Cmid, Cout, Ho, Wo;
-    int Kpad1, Kpad2;
-    int ka;                   // MFMA K-steps of the expand GEMM = ceil(Cin / 32) (<= 3)
-    int nChunks;              // ceil(Cmid / 32)
-    int nRowT;                // 16-row tiles of the project GEMM = round32(Cout) / 16
-    int tilesH, tilesW, nTiles;
-    int nbufX;                // x tile buffers (2: the next tile is prefetched)
-    int act_e, act_d, act_p, post;
-    uint32_t* ovf;            // the context's fp16 overflow counter (pcv_common.hpp, F16Guard)
-    uint32_t* dbg;            // diagnostic builds only (-DMBR_CYCLES): in-kernel stamps
-};
-
-__device__ __forceinline__ int mb_swz(int row) { return (0x78 >> (2 * ((row >> 2) & 3))) & 3; }   // [0,2,3,1]
+#include "mb_device.hpp"
 
 // Host and device agree on the LDS carve-up through this helper (offsets and total in bytes).
 struct MbLds {
@@ -69,8 +45,10 @@ static inline __host__ __device__ MbLds mb_lds_layout(int stride, bool expand, i
     return L;
 }
 
-// MAXRT: 16-row tiles of the project GEMM held in accumulators (2: Cout <= 32, 6: Cout <= 96)
-template <int DT, int S, bool EXPAND, int MAXRT>
+// The project GEMM is compiled for kMbRowT = 2 row tiles of 16 output channels (Cout <= 32: all the routing sends here; the host
+// refuses a launch whose packed projection has another row count).
+constexpr int kMbRowT = 2;
+template <int DT, int S, bool EXPAND>
 __global__ __launch_bounds__(256, 2) void mbconv_kernel(const MbParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int TH = S == 1 ? 8 : 4;                  // output rows per tile (x 16 columns)
@@ -82,7 +60,7 @@ __global__ __launch_bounds__(256, 2) void mbconv_kernel(const MbParams p) {
     constexpr int ESZ = NPT * 16 * 64;
     typedef typename Mma<DT>::frag frag;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const MbLds L = mb_lds_layout(S, EXPAND, p.ka, p.nChunks, p.nRowT, p.nbufX);
+    const MbLds L = mb_lds_layout(S, EXPAND, p.ka, p.nChunks, kMbRowT, p.nbufX);
     char* const Wes = smem + L.wexp;
     char* const Wps = smem + L.wproj;
     char* const Wds = smem + L.wdw;
@@ -124,9 +102,9 @@ __global__ __launch_bounds__(256, 2) void mbconv_kernel(const MbParams p) {
         }
     }
     {
-        const int npieces = p.nChunks * p.nRowT;                  // [chunk][nRowT x 16 rows]
+        const int npieces = p.nChunks * kMbRowT;                  // [chunk][kMbRowT x 16 rows]
         for (int pc = wave; pc < npieces; pc += 4) {
-            const int i = pc % p.nRowT, c = pc / p.nRowT;
+            const int i = pc % kMbRowT, c = pc / kMbRowT;
             const int row = 16 * i + (lane >> 2);
             const int kc = (lane & 3) ^ mb_swz(row);
             const uint32_t off = (uint32_t)((row * p.Kpad2 + 32 * c + 8 * kc) * 2);
@@ -135,7 +113,7 @@ __global__ __launch_bounds__(256, 2) void mbconv_kernel(const MbParams p) {
     }
     for (int i = tid; i < 9 * CmidP / 8; i += 256) {              // depthwise weights, 16 B = 8 channels per item
         const int t = i / (CmidP / 8), ch = (i - t * (CmidP / 8)) * 8;
-        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(wdrsrc, ch < p.Cmid ? (uint32_t)((t * p.Cmid + ch) * 2) : 0x80000000u, 0, 0);
+        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(wdrsrc, ch < p.Cmid ? (uint32_t)((t * p.Cmid + ch) * 2) : kOutOfRange, 0, 0);
         *reinterpret_cast<u32x4*>(Wds + (t * CmidP + ch) * 2) = v;
     }
     for (int i = tid; i < 4 * CmidP; i += 256) {
@@ -159,7 +137,7 @@ __global__ __launch_bounds__(256, 2) void mbconv_kernel(const MbParams p) {
             const int ch = c0 + 8 * ((lane & 3) ^ mb_swz(ip));
             const int hi = hi0 + r, wi = wi0 + c;
             const bool ok = t < p.nTiles && ip < NIP && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W && ch < p.Cin;
-            const uint32_t off = ok ? (uint32_t)(((((long)n * p.H + hi) * p.W + wi) * p.Cin + ch) * 2) : 0x80000000u;
+            const uint32_t off = ok ? (uint32_t)(((((long)n * p.H + hi) * p.W + wi) * p.Cin + ch) * 2) : kOutOfRange;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(xrsrc, PCV_LDS(dst + pc * 1024), 16, off, 0, 0, 0);
         }
     };
@@ -189,7 +167,7 @@ __global__ __launch_bounds__(256, 2) void mbconv_kernel(const MbParams p) {
     uint32_t am[4], am4[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        am[i] = ((fr >> 3) == (fq & 1) && i == ((fr & 7) >> 1)) ? 0xFFFFFFFFu : 0u;
+        am[i] = mb_diag_bit(fr, fq, i);
         am4[i] = (fq >> 1) ? 0u : am[i];
     }
     const int a_sh = (fr & 1) * 16;
@@ -200,10 +178,8 @@ __global__ __launch_bounds__(256, 2) void mbconv_kernel(const MbParams p) {
     const int tstride = gridDim.x;
 
     while (true) {
-        const int tw = tile % p.tilesW;
-        const int t2 = tile / p.tilesW;
-        const int th = t2 % p.tilesH;
-        const int n = t2 / p.tilesH;
+        int n, th, tw;
+        mb_tile_pos(tile, p.tilesW, p.tilesH, n, th, tw);
         const int ho0 = th * TH, wo0 = tw * 16;
         const int hi0 = ho0 * S - 1, wi0 = wo0 * S - 1;     // input coordinates of halo pixel (0, 0); padding = 1
         const int ntile = tile + tstride;
@@ -220,9 +196,9 @@ __global__ __launch_bounds__(256, 2) void mbconv_kernel(const MbParams p) {
             if (p.nbufX == 2) dma_x(ntile, xbuf ^ 1);            // flies during the whole chunk loop (nothing else uses vmcnt)
         }
 
-        f32x4 acc[MAXRT][NJ];
+        f32x4 acc[kMbRowT][NJ];
 #pragma unroll
-        for (int i = 0; i < MAXRT; ++i)
+        for (int i = 0; i < kMbRowT; ++i)
 #pragma unroll
             for (int jj = 0; jj < NJ; ++jj) acc[i][jj] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
@@ -291,12 +267,7 @@ __global__ __launch_bounds__(256, 2) void mbconv_kernel(const MbParams p) {
 #pragma unroll
                 for (int j = 0; j < 5; ++j) {
                     // (the last pair's second tap reads the 16 bits behind the table - still this block's LDS - and is masked off)
-                    const uint32_t w16 = *reinterpret_cast<const uint16_t*>(Wds + a_woff + (2 * j * CmidP + 32 * c) * 2);
-                    const uint32_t val = w16 << a_sh;
-                    u32x4 a4;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) a4[i] = val & (j < 4 ? am[i] : am4[i]);
-                    af[j] = __builtin_bit_cast(frag, a4);
+                    af[j] = mb_diag_frag<frag>(Wds + a_woff + (2 * j * CmidP + 32 * c) * 2, a_sh, j < 4 ? am : am4);
                 }
                 const f32x4 sd = *reinterpret_cast<const f32x4*>(BNs + 2 * CmidP + 32 * c + 16 * dg + 4 * fq);
                 const f32x4 hd = *reinterpret_cast<const f32x4*>(BNs + 3 * CmidP + 32 * c + 16 * dg + 4 * fq);
@@ -325,18 +296,16 @@ __global__ __launch_bounds__(256, 2) void mbconv_kernel(const MbParams p) {
             g2.commit(p.ovf);
             // ---- S3: project GEMM, K-step = this chunk --------------------------------------------------------------------------
             {
-                frag wp[MAXRT];
+                frag wp[kMbRowT];
 #pragma unroll
-                for (int i = 0; i < MAXRT; ++i)
-                    if (i < p.nRowT)
-                        wp[i] = *reinterpret_cast<const frag*>(Wps + ((c * p.nRowT + i) * 16 + fr) * 64 + ((fq ^ mb_swz(fr)) << 4));
+                for (int i = 0; i < kMbRowT; ++i)
+                    wp[i] = *reinterpret_cast<const frag*>(Wps + ((c * kMbRowT + i) * 16 + fr) * 64 + ((fq ^ mb_swz(fr)) << 4));
 #pragma unroll
                 for (int jj = 0; jj < NJ; ++jj) {
                     const int op = 16 * (NJ * wave + jj) + fr;
                     const frag b = *reinterpret_cast<const frag*>(Ds + op * 64 + ((fq ^ mb_swz(op)) << 4));
 #pragma unroll
-                    for (int i = 0; i < MAXRT; ++i)
-                        if (i < p.nRowT) acc[i][jj] = Mma<DT>::run(wp[i], b, acc[i][jj]);
+                    for (int i = 0; i < kMbRowT; ++i) acc[i][jj] = Mma<DT>::run(wp[i], b, acc[i][jj]);
                 }
             }
             // (the next chunk's S1 writes E, which nobody reads after the barrier above; its barrier orders S3 against the next S2)
@@ -345,44 +314,33 @@ __global__ __launch_bounds__(256, 2) void mbconv_kernel(const MbParams p) {
         // ---- epilogue: BN (+ residual), 16-byte NHWC stores --------------------------------------------------------------------
         F16Guard<DT> guard;
 #pragma unroll
-        for (int ipp = 0; ipp < MAXRT / 2; ++ipp) {
-            if (2 * ipp < p.nRowT) {
-                const int ch = 32 * ipp + 8 * fq;
-                f32x4 sp[2], hp[2];
+        for (int ipp = 0; ipp < kMbRowT / 2; ++ipp) {
+            const int ch = 32 * ipp + 8 * fq;
+            f32x4 sp[2], hp[2];
 #pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    sp[h] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(sprsrc, (uint32_t)((ch + 4 * h) * 4), 0, 0));
-                    hp[h] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(hprsrc, (uint32_t)((ch + 4 * h) * 4), 0, 0));
+            for (int h = 0; h < 2; ++h) {
+                sp[h] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(sprsrc, (uint32_t)((ch + 4 * h) * 4), 0, 0));
+                hp[h] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(hprsrc, (uint32_t)((ch + 4 * h) * 4), 0, 0));
+            }
+#pragma unroll
+            for (int jj = 0; jj < NJ; ++jj) {
+                const int ho = ho0 + NJ * wave + jj, wo = wo0 + fr;
+                const bool ok = ch < p.Cout && ho < p.Ho && wo < p.Wo;
+                const uint32_t off = ok ? mb_out_off(p, n, ho, wo, ch) : kOutOfRange;
+                float v[8];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    v[e] = acc[2 * ipp][jj][e] * sp[0][e] + hp[0][e];
+                    v[4 + e] = acc[2 * ipp + 1][jj][e] * sp[1][e] + hp[1][e];
                 }
+                apply_act8(v, act_p);
+                if (p.res != nullptr) add_skip8<DT>(v, __builtin_amdgcn_raw_buffer_load_b128(rrsrc, off, 0, 0));
+                apply_act8(v, post);                                // post_act also without a skip tensor, as the separate launches
+                guard.see(v);
+                u32x4 o;
 #pragma unroll
-                for (int jj = 0; jj < NJ; ++jj) {
-                    const int ho = ho0 + NJ * wave + jj, wo = wo0 + fr;
-                    const bool ok = ch < p.Cout && ho < p.Ho && wo < p.Wo;
-                    const uint32_t off = ok ? (uint32_t)(((((long)n * p.Ho + ho) * p.Wo + wo) * p.Cout + ch) * 2) : 0x80000000u;
-                    float v[8];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        v[e] = acc[2 * ipp][jj][e] * sp[0][e] + hp[0][e];
-                        v[4 + e] = acc[2 * ipp + 1][jj][e] * sp[1][e] + hp[1][e];
-                    }
-                    apply_act8(v, act_p);
-                    if (p.res != nullptr) {
-                        const u32x4 rv = __builtin_amdgcn_raw_buffer_load_b128(rrsrc, off, 0, 0);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            float r0, r1;
-                            unpack2<DT>(rv[e], r0, r1);
-                            v[2 * e] += r0;
-                            v[2 * e + 1] += r1;
-                        }
-                    }
-                    apply_act8(v, post);                                // post_act also without a skip tensor, as the separate launches
-                    guard.see(v);
-                    u32x4 o;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = pack2<DT>(v[2 * e], v[2 * e + 1]);
-                    __builtin_amdgcn_raw_buffer_store_b128(o, yrsrc, off, 0, 0);
-                }
+                for (int e = 0; e < 4; ++e) o[e] = pack2<DT>(v[2 * e], v[2 * e + 1]);
+                __builtin_amdgcn_raw_buffer_store_b128(o, yrsrc, off, 0, 0);
             }
         }
 

@@ -31,9 +31,7 @@
 // LDS holds only what every wave reads: the 1x1 weights (64-byte swizzled rows as in mbw.hpp), the diagonal fragments, BN constants.
 #pragma once
 #include <type_traits>
-#include "pcv_common.hpp"
-#include "mbconv.hpp"         // MbParams
-#include "mbw.hpp"            // mbw_swz, mbw_act
+#include "mb_device.hpp"
 
 struct MbrLds {
     int wexp, wproj, af, bn, bnp, xs, total;
@@ -181,12 +179,12 @@ __global__ __launch_bounds__(64 * WAVES) void mbr_kernel(const MbParams p) {
                     const int slot = i & 3, r = (i >> 2) & 31, ks = (i >> 7) % KA, c = (i >> 7) / KA;
                     const uint32_t off = (uint32_t)(((32 * c + r) * p.Kpad1 + 32 * ks + 8 * slot) * 2);
                     src = static_cast<const char*>(p.w_exp) + off; ok = off + 16u <= p.wexp_bytes;
-                    dst[k] = Wes + ((c * KA + ks) * 32 + r) * 64 + ((slot ^ mbw_swz<true>(r)) << 4);
+                    dst[k] = Wes + ((c * KA + ks) * 32 + r) * 64 + ((slot ^ mb_swz64<true>(r)) << 4);
                 } else if ((i -= nA) < nB) {                                       // projection weights: K slice 32 c of every row
                     const int slot = i & 3, row = (i >> 2) % (NRT * 16), c = (i >> 2) / (NRT * 16);
                     const uint32_t off = (uint32_t)((row * p.Kpad2 + 32 * c + 8 * slot) * 2);
                     src = static_cast<const char*>(p.w_proj) + off; ok = off + 16u <= p.wproj_bytes;
-                    dst[k] = Wps + (c * NRT * 16 + row) * 64 + ((slot ^ mbw_swz<true>(row)) << 4);
+                    dst[k] = Wps + (c * NRT * 16 + row) * 64 + ((slot ^ mb_swz64<true>(row)) << 4);
                 } else if ((i -= nB) < nC) {                                       // compressed depthwise fragments, as packed
                     src = static_cast<const char*>(p.w_dwsp) + i * 16; ok = true;
                     dst[k] = Afs + i * 16;
@@ -224,7 +222,7 @@ __global__ __launch_bounds__(64 * WAVES) void mbr_kernel(const MbParams p) {
 #endif
     const ActClamp act_e = make_act(p.act_e), act_d = make_act(p.act_d), act_p = make_act(p.act_p), post = make_act(p.post);
 
-    const int fsw = (fq ^ mbw_swz<true>(fr)) << 4;                                   // fragment access of row (16 k + fr), slot fq
+    const int fsw = (fq ^ mb_swz64<true>(fr)) << 4;                                   // fragment access of row (16 k + fr), slot fq
     const char* const we_rd = Wes + fr * 64 + fsw;
     const char* const wp_rd = Wps + fr * 64 + fsw;
     const char* const af_rd = Afs + lane * 16;
@@ -243,10 +241,8 @@ __global__ __launch_bounds__(64 * WAVES) void mbr_kernel(const MbParams p) {
     struct TilePos { int n, h0, wi; bool colok, colok1; int off0; };        // (PS: wi / colok / off0 of the EVEN block; the odd block is one column to the left)
     auto decode = [&](int t) __attribute__((always_inline)) -> TilePos {
         TilePos T;
-        const int tw = t % p.tilesW;
-        const int t2 = t / p.tilesW;
-        const int th = t2 % p.tilesH;
-        T.n = t2 / p.tilesH;
+        int th, tw;
+        mb_tile_pos(t, p.tilesW, p.tilesH, T.n, th, tw);
         T.h0 = th * RO;                                                             // first OUTPUT row
         T.wi = PS ? tw * OC * 2 + 2 * fr : tw * OC * S - 1 + fr;                   // this lane's INPUT column
         T.colok = (t < p.nTiles) & ((unsigned)T.wi < (unsigned)p.W);
@@ -258,7 +254,7 @@ __global__ __launch_bounds__(64 * WAVES) void mbr_kernel(const MbParams p) {
     // x fragment of window row r (window rows h0 - 1 .. h0 + RO, columns w0 - 1 .. w0 + 14)
     auto load_x = [&](const TilePos& T, int r, int b, int ks) __attribute__((always_inline)) -> u32x4 {        // (b: 0 = the block / the even block, 1 = the odd block)
         const bool ok = (b ? T.colok1 : T.colok) & ((unsigned)(T.h0 * S - 1 + r) < (unsigned)p.H) & (32 * ks + 8 * fq < p.Cin);
-        return __builtin_amdgcn_raw_buffer_load_b128(xrsrc, ok ? (uint32_t)(T.off0 - b * p.Cin * 2 + r * rowpitch + 64 * ks) : 0x80000000u, 0, 0);
+        return __builtin_amdgcn_raw_buffer_load_b128(xrsrc, ok ? (uint32_t)(T.off0 - b * p.Cin * 2 + r * rowpitch + 64 * ks) : kOutOfRange, 0, 0);
     };
 
     // fragments of half-chunk pass h = 2 c + g that do not live in LDS
@@ -290,7 +286,7 @@ __global__ __launch_bounds__(64 * WAVES) void mbr_kernel(const MbParams p) {
         for (int r = 0; r < NR; ++r) {
             const bool ok = T.colok & ((unsigned)(T.h0 * S - 1 + r) < (unsigned)p.H) & (8 * fq < p.Cin);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(xrsrc, (lds_char*)(size_t)PCV_LDS(xs + (buf * NR + r) * 1024), 16,
-                                                     ok ? (uint32_t)(T.off0 + r * rowpitch) : 0x80000000u, 0, 0, 0);
+                                                     ok ? (uint32_t)(T.off0 + r * rowpitch) : kOutOfRange, 0, 0, 0);
         }
     };
     int xbuf = 0;
@@ -480,7 +476,7 @@ __global__ __launch_bounds__(64 * WAVES) void mbr_kernel(const MbParams p) {
                             float v[4];
 #pragma unroll
                             for (int e = 0; e < 4; ++e) v[e] = __builtin_fmaf(da[u][e], sd[e], hd[e]);
-                            mbw_act<ACT, 4>(v, act_d);
+                            mb_act<ACT, 4>(v, act_d);
                             if constexpr (ACT != PCV_ACT_RELU6 && (MBR_DBG & 256) == 0) g2.see(v);
                             od[0] = pack2<DT>(v[0], v[1]);
                             od[1] = pack2<DT>(v[2], v[3]);
@@ -527,25 +523,15 @@ __global__ __launch_bounds__(64 * WAVES) void mbr_kernel(const MbParams p) {
             for (int u = 0; u < RO; ++u) {
                 const int ho = h0 + u;
                 const bool ok = lane_out & (ch < p.Cout) & (ho < p.Ho) & (wo < p.Wo);
-                const uint32_t off = ok ? (uint32_t)(((((long)n * p.Ho + ho) * p.Wo + wo) * p.Cout + ch) * 2) : 0x80000000u;
+                const uint32_t off = ok ? mb_out_off(p, n, ho, wo, ch) : kOutOfRange;
                 float v[8];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    v[e] = acc[2 * ipp][u][e] * sp[0][e] + hp[0][e];
-                    v[4 + e] = acc[2 * ipp + 1][u][e] * sp[1][e] + hp[1][e];
-                }
+                bn8(v, acc[2 * ipp][u], acc[2 * ipp + 1][u], sp[0], sp[1], hp[0], hp[1]);
                 if constexpr (!decltype(plain)::value) apply_act8(v, act_p);
                 if (p.res != nullptr) {                                  // (x as the skip tensor: channels 32 ipp + 8 fq = K step ipp of window row u + 1)
                     u32x4 r4;
                     if constexpr (XL) r4 = resx ? *reinterpret_cast<const u32x4*>(xrd + (u + 1) * 1024) : __builtin_amdgcn_raw_buffer_load_b128(rrsrc, off, 0, 0);
                     else r4 = resx ? xr[S == 1 ? u + 1 : 0][0][ipp < KA ? ipp : 0] : __builtin_amdgcn_raw_buffer_load_b128(rrsrc, off, 0, 0);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float r0, r1;
-                        unpack2<DT>(r4[e], r0, r1);
-                        v[2 * e] += r0;
-                        v[2 * e + 1] += r1;
-                    }
+                    add_skip8<DT>(v, r4);
                 }
                 if constexpr (!decltype(plain)::value) apply_act8(v, post);          // post_act also without a skip tensor, as the separate launches
 

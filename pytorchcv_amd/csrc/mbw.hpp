@@ -26,8 +26,7 @@
 // LDS busy 47-67 % of the kernel's time.) The 2 x 8 pixel blocks read two runs of 8 rows and stay 2-4-way conflicted unless the
 // runs are 8 k rows apart; they are kept selectable, the default is 1 x 16.
 #pragma once
-#include "pcv_common.hpp"
-#include "mbconv.hpp"         // MbParams
+#include "mb_device.hpp"
 
 struct MbwLds {
     int wexp, wproj, wdw, bn, wave0, per_wave, total;
@@ -55,22 +54,6 @@ static inline __host__ __device__ MbwLds mbw_lds_layout(int stride, int nrt, int
     o += nWaves * L.per_wave;
     L.total = o;
     return L;
-}
-
-template <bool SWZ> __device__ __forceinline__ int mbw_swz(int row) { return SWZ ? (row >> 1) & 2 : 0; }      // slot XOR of a 64-byte LDS row
-
-// The activation behind the expand and the depthwise stage as a compile-time constant: with the launch-time code every one of the
-// 11 + 4 unrolled applications per chunk was a nest of scalar branches (580 basic blocks), and nothing could be scheduled across them.
-template <int ACT, int N> __device__ __forceinline__ void mbw_act(float (&v)[N], const ActClamp& dyn) {
-    if constexpr (ACT == PCV_ACT_RELU) {
-#pragma unroll
-        for (int e = 0; e < N; ++e) v[e] = __builtin_elementwise_maximum(v[e], 0.f);
-    } else if constexpr (ACT == PCV_ACT_RELU6) {
-#pragma unroll
-        for (int e = 0; e < N; ++e) v[e] = __builtin_elementwise_minimum(__builtin_elementwise_maximum(v[e], 0.f), 6.f);
-    } else {
-        apply_actn<N>(v, dyn);
-    }
 }
 
 // S: stride; NRT: 16-row tiles of the project GEMM (2: Cout <= 32, 4: Cout <= 64); ACT: activation of the expand and depthwise
@@ -131,16 +114,16 @@ __global__ __launch_bounds__(512) void mbw_kernel(const MbParams p) {
     for (int i = tid; WLDS && i < p.nChunks * 32 * 4; i += blockDim.x) {
         const int slot = i & 3, row = i >> 2;                                      // row = 32 c + r: packed row order = MFMA order
         const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(wersrc, (uint32_t)((row * p.Kpad1 + 8 * slot) * 2), 0, 0);
-        *reinterpret_cast<u32x4*>(Wes + row * PITCH + ((slot ^ mbw_swz<SWZ>(row)) << 4)) = v;
+        *reinterpret_cast<u32x4*>(Wes + row * PITCH + ((slot ^ mb_swz64<SWZ>(row)) << 4)) = v;
     }
     for (int i = tid; WLDS && i < p.nChunks * NRT * 16 * 4; i += blockDim.x) {
         const int slot = i & 3, row = (i >> 2) % (NRT * 16), c = (i >> 2) / (NRT * 16);
         const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(wprsrc, (uint32_t)((row * p.Kpad2 + 32 * c + 8 * slot) * 2), 0, 0);
-        *reinterpret_cast<u32x4*>(Wps + (c * NRT * 16 + row) * PITCH + ((slot ^ mbw_swz<SWZ>(row)) << 4)) = v;
+        *reinterpret_cast<u32x4*>(Wps + (c * NRT * 16 + row) * PITCH + ((slot ^ mb_swz64<SWZ>(row)) << 4)) = v;
     }
     for (int i = tid; i < 10 * CmidP / 8; i += blockDim.x) {
         const int t = i / (CmidP / 8), ch = (i - t * (CmidP / 8)) * 8;
-        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(wdrsrc, (t < 9 && ch < p.Cmid) ? (uint32_t)((t * p.Cmid + ch) * 2) : 0x80000000u, 0, 0);
+        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(wdrsrc, (t < 9 && ch < p.Cmid) ? (uint32_t)((t * p.Cmid + ch) * 2) : kOutOfRange, 0, 0);
         *reinterpret_cast<u32x4*>(Wds + (t * CmidP + ch) * 2) = v;
     }
     for (int i = tid; i < 4 * CmidP; i += blockDim.x) {
@@ -168,7 +151,7 @@ __global__ __launch_bounds__(512) void mbw_kernel(const MbParams p) {
     const int pr = fr / TW, pc = fr % TW;                                          // this lane's pixel inside a pixel block
     uint32_t am[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) am[i] = ((fr >> 3) == (fq & 1) && i == ((fr & 7) >> 1)) ? 0xFFFFFFFFu : 0u;
+    for (int i = 0; i < 4; ++i) am[i] = mb_diag_bit(fr, fq, i);
     const int a_sh = (fr & 1) * 16;
     const char* const a_w = Wds + ((fq >> 1) * CmidP + fr) * 2;                    // + (2 j CmidP + 32 c + 16 g) * 2
     // S2 read addresses (channel half g = 0; g = 1 is the address ^ 32 = + 32 without the swizzle): one register per (pixel block,
@@ -182,14 +165,14 @@ __global__ __launch_bounds__(512) void mbw_kernel(const MbParams p) {
             const int tap = min(2 * j + (fq >> 1), 8);                             // tap 9 has zero weights: any valid address
             const int wr = (u + R * pr) * S + tap / 3, wcol = pc * S + tap % 3;       // pixel block u = output rows u (and u + R)
             const int sidx = wr * IWS + (S == 1 ? wcol : (wcol & 1) * IWH + (wcol >> 1));
-            boff[u][j] = (uint32_t)(sidx * PITCH + (((fq & 1) ^ mbw_swz<SWZ>(sidx)) << 4));
+            boff[u][j] = (uint32_t)(sidx * PITCH + (((fq & 1) ^ mb_swz64<SWZ>(sidx)) << 4));
         }
-    const int fsw = (fq ^ mbw_swz<SWZ>(fr)) << 4;                                       // fragment access of row (16 k + fr), slot fq
+    const int fsw = (fq ^ mb_swz64<SWZ>(fr)) << 4;                                       // fragment access of row (16 k + fr), slot fq
     const char* const e_wr = Es + fr * PITCH + fsw;                                // S1 writes: + 16 m * PITCH
     const char* const d_rd = Ds + fr * PITCH + fsw;
     // D write: 8 bytes = channels 16 g + 4 fq .. + 3 of pixel (16 u + fr) = slot 2 g + (fq >> 1), half fq & 1; g = 1 is ^ 32
-    char* const d_wr0 = Ds + fr * PITCH + ((((fq >> 1) ^ mbw_swz<SWZ>(fr))) << 4) + 8 * (fq & 1);
-    char* const d_wr1 = Ds + fr * PITCH + ((((2 + (fq >> 1)) ^ mbw_swz<SWZ>(fr))) << 4) + 8 * (fq & 1);
+    char* const d_wr0 = Ds + fr * PITCH + ((((fq >> 1) ^ mb_swz64<SWZ>(fr))) << 4) + 8 * (fq & 1);
+    char* const d_wr1 = Ds + fr * PITCH + ((((2 + (fq >> 1)) ^ mb_swz64<SWZ>(fr))) << 4) + 8 * (fq & 1);
     const char* const we_rd = Wes + fr * PITCH + fsw;
     const char* const wp_rd = Wps + fr * PITCH + fsw;
 
@@ -198,10 +181,8 @@ __global__ __launch_bounds__(512) void mbw_kernel(const MbParams p) {
 
     // ---- x fragments of tile t: global -> registers ---------------------------------------------------------------------------------
     auto load_x = [&](int t, u32x4 (&xr)[KA][NPT], uint32_t& vmask) __attribute__((always_inline)) {
-        const int tw = t % p.tilesW;
-        const int t2 = t / p.tilesW;
-        const int th = t2 % p.tilesH;
-        const int n = t2 / p.tilesH;
+        int n, th, tw;
+        mb_tile_pos(t, p.tilesW, p.tilesH, n, th, tw);
         const int hi0 = th * RO * S - 1, wi0 = tw * TW * S - 1;
         const bool live = t < p.nTiles;
         vmask = 0;
@@ -213,7 +194,7 @@ __global__ __launch_bounds__(512) void mbw_kernel(const MbParams p) {
             const uint32_t off = (uint32_t)((((n * p.H + hi) * p.W + wi) * p.Cin + 8 * fq) * 2);        // < 2 GiB: checked by the host
 #pragma unroll
             for (int ks = 0; ks < KA; ++ks)
-                xr[ks][m] = __builtin_amdgcn_raw_buffer_load_b128(xrsrc, (ok & (32 * ks + 8 * fq < p.Cin)) ? off + 64 * ks : 0x80000000u, 0, 0);
+                xr[ks][m] = __builtin_amdgcn_raw_buffer_load_b128(xrsrc, (ok & (32 * ks + 8 * fq < p.Cin)) ? off + 64 * ks : kOutOfRange, 0, 0);
         }
     };
 
@@ -229,10 +210,8 @@ __global__ __launch_bounds__(512) void mbw_kernel(const MbParams p) {
         if constexpr (XPRE) load_x(ntile, xb, vmn);                                // in flight during the whole tile
         else load_x(tile, xa, vm);
 
-        const int tw = tile % p.tilesW;
-        const int t2 = tile / p.tilesW;
-        const int th = t2 % p.tilesH;
-        const int n = t2 / p.tilesH;
+        int n, th, tw;
+        mb_tile_pos(tile, p.tilesW, p.tilesH, n, th, tw);
         const int ho0 = th * RO, wo0 = tw * TW;
 
         f32x4 acc[NRT][R];
@@ -343,12 +322,7 @@ __global__ __launch_bounds__(512) void mbw_kernel(const MbParams p) {
                 frag af[5];
 #pragma unroll
                 for (int j = 0; j < 5; ++j) {
-                    const uint32_t w16 = *reinterpret_cast<const uint16_t*>(a_w + (2 * j * CmidP + 32 * c + 16 * g) * 2);
-                    const uint32_t val = w16 << a_sh;
-                    u32x4 a4;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) a4[i] = val & am[i];
-                    af[j] = __builtin_bit_cast(frag, a4);
+                    af[j] = mb_diag_frag<frag>(a_w + (2 * j * CmidP + 32 * c + 16 * g) * 2, a_sh, am);
                 }
                 const f32x4 sd = *reinterpret_cast<const f32x4*>(BNs + 2 * CmidP + 32 * c + 16 * g + 4 * fq);
                 const f32x4 hd = *reinterpret_cast<const f32x4*>(BNs + 3 * CmidP + 32 * c + 16 * g + 4 * fq);
@@ -374,7 +348,7 @@ __global__ __launch_bounds__(512) void mbw_kernel(const MbParams p) {
                         o[0] = pack2_clamp_f16(v[0], v[1], 0x46004600u);
                         o[1] = pack2_clamp_f16(v[2], v[3], 0x46004600u);
                     } else {
-                        mbw_act<ACT, 4>(v, act_d);
+                        mb_act<ACT, 4>(v, act_d);
                         if constexpr (ACT != PCV_ACT_RELU6) g2.see(v);
                         o[0] = pack2<DT>(v[0], v[1]);
                         o[1] = pack2<DT>(v[2], v[3]);
@@ -418,7 +392,7 @@ __global__ __launch_bounds__(512) void mbw_kernel(const MbParams p) {
             for (int u = 0; u < R; ++u) {
                 const int ho = ho0 + u + R * pr, wo = wo0 + pc;
                 const bool ok = ch < p.Cout && ho < p.Ho && wo < p.Wo;
-                const uint32_t off = ok ? (uint32_t)(((((long)n * p.Ho + ho) * p.Wo + wo) * p.Cout + ch) * 2) : 0x80000000u;
+                const uint32_t off = ok ? mb_out_off(p, n, ho, wo, ch) : kOutOfRange;
                 float v[8];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -426,16 +400,7 @@ __global__ __launch_bounds__(512) void mbw_kernel(const MbParams p) {
                     v[4 + e] = acc[2 * ipp + 1][u][e] * sp[1][e] + hp[1][e];
                 }
                 apply_act8(v, act_p);
-                if (p.res != nullptr) {
-                    const u32x4 rv = __builtin_amdgcn_raw_buffer_load_b128(rrsrc, off, 0, 0);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float r0, r1;
-                        unpack2<DT>(rv[e], r0, r1);
-                        v[2 * e] += r0;
-                        v[2 * e + 1] += r1;
-                    }
-                }
+                if (p.res != nullptr) add_skip8<DT>(v, __builtin_amdgcn_raw_buffer_load_b128(rrsrc, off, 0, 0));
                 apply_act8(v, post);                                    // post_act also without a skip tensor, as the separate launches
                 guard.see(v);
                 u32x4 o;

@@ -662,16 +662,16 @@ static const char* pair_unsupported(const pcv_conv_desc& a, const pcv_conv_desc&
 
 // ---- fused inverted-residual unit (mbconv.hpp) ----------------------------------------------------------------------------
 typedef void (*mbconv_fn)(const MbParams);
-template <int DT, int RT> static mbconv_fn mbconv_for(int stride, bool expand) {
-    if (stride == 1) return expand ? mbconv_kernel<DT, 1, true, RT> : mbconv_kernel<DT, 1, false, RT>;
-    return expand ? mbconv_kernel<DT, 2, true, RT> : mbconv_kernel<DT, 2, false, RT>;
+template <int DT> static mbconv_fn mbconv_for(int stride, bool expand) {
+    if (stride == 1) return expand ? mbconv_kernel<DT, 1, true> : mbconv_kernel<DT, 1, false>;
+    return expand ? mbconv_kernel<DT, 2, true> : mbconv_kernel<DT, 2, false>;
 }
 // The three fused-unit kernels size their LDS per unit (mbconv_plan / mbw_lds_layout / mbr_entry_lds): the launch passes that size as
 // `lds`, the default is the limit every instantiation is enabled for.
 static const int kMbMaxLds = 150 * 1024, kMbwMaxLds = 160 * 1024;
-static Kernel mbconv_kernel(int dt, int stride, bool expand, int nrowt, int lds = kMbMaxLds) {
-    if (dt == PCV_BF16) return kernel_of(nrowt <= 2 ? mbconv_for<PCV_BF16, 2>(stride, expand) : mbconv_for<PCV_BF16, 6>(stride, expand), 256, lds);
-    return kernel_of(nrowt <= 2 ? mbconv_for<PCV_F16, 2>(stride, expand) : mbconv_for<PCV_F16, 6>(stride, expand), 256, lds);
+// block tiles (mbconv.hpp): compiled for kMbRowT = 2 projection row tiles, i.e. Cout <= 32
+static Kernel mbconv_kernel(int dt, int stride, bool expand, int lds = kMbMaxLds) {
+    return kernel_of(dt == PCV_BF16 ? mbconv_for<PCV_BF16>(stride, expand) : mbconv_for<PCV_F16>(stride, expand), 256, lds);
 }
 // wave-private variant (mbw.hpp): Cin <= 32, Cout <= 64
 struct MbwEntry { int dt, s, nrt, act, tw, ka, rb; mbconv_fn fn; };
@@ -784,8 +784,7 @@ static int enable_kernels(pcv_ctx* ctx) {
         }
     for (int dt = PCV_BF16; dt <= PCV_F16; ++dt)
         for (int s = 1; s <= 2; ++s)
-            for (int e = 0; e < 2; ++e)
-                for (int rt = 2; rt <= 6; rt += 4) on(mbconv_kernel(dt, s, e != 0, rt));
+            for (int e = 0; e < 2; ++e) on(mbconv_kernel(dt, s, e != 0));
     for (const MbwEntry& e : kMbw) on(mbw_kernel_of(e));
     for (const MbrEntry& e : kMbr) on(mbr_kernel_of(e));
     on(classify_kernel_of(1024));
@@ -2326,7 +2325,7 @@ int pcv_mbconv_fused(pcv_ctx* ctx, const pcv_conv_desc* d_exp, const pcv_conv_de
     p.tilesH = (p.Ho + TH - 1) / TH; p.tilesW = (p.Wo + 15) / 16;
     p.nTiles = p.N * p.tilesH * p.tilesW;
     p.act_e = d_exp ? d_exp->act : 0; p.act_d = d_dw->act; p.act_p = d_proj->act; p.post = d_proj->post_act;
-    if (p.nRowT > 6 || (d_exp && p.Kpad1 < 32 * p.ka) || p.Kpad2 < 32 * p.nChunks)
+    if ((d_exp && p.Kpad1 < 32 * p.ka) || p.Kpad2 < 32 * p.nChunks)
         return fail(ctx, PCV_ERR_INVALID, "pcv_mbconv_fused: unexpected packed layout");
     // wave-private tiles (mbw.hpp) where the unit qualifies; pcv_set_tuning("mbw", 0) sends the shapes BOTH kernels cover to mbconv.hpp
     int kaw = 0, nrt = 0, rbw = 0;
@@ -2367,8 +2366,13 @@ int pcv_mbconv_fused(pcv_ctx* ctx, const pcv_conv_desc* d_exp, const pcv_conv_de
             return launch(ctx, mbw_kernel_of(*ew, nw, wl.total), gridw, (hipStream_t)stream, p);
         }
     }
-    const MbLds lds = mbconv_plan(S, d_exp != nullptr, p.ka, p.nChunks, p.nRowT, &p.nbufX);
-    const Kernel K = mbconv_kernel(d_dw->dtype, S, d_exp != nullptr, p.nRowT, lds.total);
+    // block tiles (mbconv.hpp). Every unit that gets here has Cout <= 32: without a wave shape mbconv_unsupported admits no more, with
+    // one the branch above is left only when mbw is switched off and block_shape holds (mbw_waves cannot return 0 for an admitted
+    // unit: its window blocks are the same for both pixel-block widths, and mbconv_unsupported checked the 1 x 16 form). The kernel is
+    // compiled for exactly that, so anything else is refused, not launched.
+    if (p.nRowT != kMbRowT) return fail(ctx, PCV_ERR_INVALID, "pcv_mbconv_fused: unexpected packed layout");
+    const MbLds lds = mbconv_plan(S, d_exp != nullptr, p.ka, p.nChunks, kMbRowT, &p.nbufX);
+    const Kernel K = mbconv_kernel(d_dw->dtype, S, d_exp != nullptr, lds.total);
     int nb = 0;                 // (per launch: the resident blocks depend on the unit's LDS plan)
     if (int rc = blocks_per_cu(ctx, K, &nb)) return rc;
     const unsigned grid = (unsigned)std::min<long>(p.nTiles, (long)block_slots(ctx, nb));

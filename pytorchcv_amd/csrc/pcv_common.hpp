@@ -261,6 +261,27 @@ template <int N> __device__ __forceinline__ void apply_actn(float (&v)[N], const
 __device__ __forceinline__ void clamp8(float (&v)[8], const ActClamp& a) { clampn<8>(v, a); }
 __device__ __forceinline__ void apply_act8(float (&v)[8], const ActClamp& a) { apply_actn<8>(v, a); }
 
+// ---- eight values of an epilogue: the 8 consecutive channels of one pixel that a lane owns (accumulators c0: + 0..3, c1: + 4..7) ----------
+// v = acc * scale + shift, and the 16 bytes of a skip tensor added to it. Straight-line steps; the sequence around them (activations,
+// range check, pack, store) stays in each kernel (conv_device.hpp, mb_device.hpp).
+__device__ __forceinline__ void bn8(float (&v)[8], const f32x4& c0, const f32x4& c1, const f32x4& s0, const f32x4& s1, const f32x4& h0,
+                                    const f32x4& h1) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        v[e] = c0[e] * s0[e] + h0[e];
+        v[4 + e] = c1[e] * s1[e] + h1[e];
+    }
+}
+template <int DT> __device__ __forceinline__ void add_skip8(float (&v)[8], const u32x4& skip) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float lo, hi;
+        unpack2<DT>(skip[e], lo, hi);
+        v[2 * e] += lo;
+        v[2 * e + 1] += hi;
+    }
+}
+
 // ---- exact unsigned division by a launch-time constant, n < 2^31 ----------------------------------------
 struct FastDiv {
     uint32_t d, magic, shift;

@@ -211,7 +211,8 @@ def route(u, k):
     ka = (u.Cin + 31) // 32 if u.expand else 0
     nRowT = (u.Cout + 31) // 32 * 2
     nbuf, lds = mbconv_plan(S, u.expand, ka, nChunks, nRowT)
-    return Route("blk", (S, u.expand, 2 if nRowT <= 2 else 6), 8 if S == 1 else 4, 16, 4, lds, nbuf)
+    assert nRowT == 2, u                                    # the block kernel is compiled for Cout <= 32 (pcv_mbconv_fused refuses the rest)
+    return Route("blk", (S, u.expand), 8 if S == 1 else 4, 16, 4, lds, nbuf)
 
 
 # ---- cases ----------------------------------------------------------------------------------------------------------------------------
@@ -242,11 +243,13 @@ _MBW_GEOM = [
     (40, 72, 64, 1, 3, 9, 17), (64, 200, 40, 1, 2, 8, 24),
 ]
 _MBW_WIDE = [(64, 144, 96, 1, 3, 9, 17), (72, 200, 72, 1, 2, 9, 25), (96, 576, 96, 1, 2, 8, 16)]
-# block tiles: Cout <= 32 and Wo >= 24; with and without the expand stage, ka = 1 / 2 / 3
+# block tiles: Cout <= 32 and Wo >= 24; with and without the expand stage, ka = 1 / 2 / 3; Cout = 16 (half of the second projection row
+# tile is padding) is what MobileNetV3's first unit runs
 _BLK_GEOM = [
     (24, 40, 24, 1, 3, 9, 33, True), (32, 72, 32, 1, 2, 8, 24, True), (8, 8, 8, 1, 2, 9, 32, True), (24, 40, 24, 2, 3, 17, 65, True),
     (32, 144, 8, 2, 2, 16, 48, True), (64, 144, 32, 1, 2, 8, 24, True), (96, 200, 24, 1, 3, 9, 33, True), (72, 72, 8, 2, 2, 17, 48, True),
     (40, 40, 24, 1, 2, 9, 33, False), (72, 72, 32, 2, 3, 18, 64, False), (8, 8, 8, 1, 2, 8, 24, False),
+    (16, 16, 16, 1, 2, 9, 33, False), (16, 72, 16, 2, 2, 17, 48, True),
 ]
 
 

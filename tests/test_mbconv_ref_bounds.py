@@ -334,9 +334,8 @@ def _lds_grid():
                 rows.add(("mbw", s, nrt, nChunks, nw, tw, ka, rb))
         for s in (1, 2):
             for expand, ka in ((0, 0), (1, 1), (1, 2), (1, 3)):
-                for nRowT in (2, 6):
-                    for nbuf in (1, 2):
-                        rows.add(("mb", s, expand, ka, nChunks, nRowT, nbuf))
+                for nbuf in (1, 2):
+                    rows.add(("mb", s, expand, ka, nChunks, 2, nbuf))               # the block kernel's row tiles: the constant kMbRowT
     return sorted(rows)
 
 
@@ -375,14 +374,17 @@ def test_routing_of_known_units():
 
 # ---- 6. coverage -------------------------------------------------------------------------------------------------------------------------------
 def test_case_lists_reach_every_reachable_instance():
+    """every instance of the three kernels: since the block kernel lost its six-row-tile variants, none is unreachable"""
     reached = {(route(c.u, c.k).kernel, route(c.u, c.k).inst) for c in EXACT + BOUNDED}
     for c in EXACT + BOUNDED:
         assert unsupported(c.u) is None and route(c.u, c.k).kernel == c.want, case_id(c)
     mbr = {("mbr", (a,) + row) for a in (RELU, RELU6) for row in S.MBR_ROWS}
     mbw = {("mbw", (a,) + row) for a in (-1, RELU, RELU6) for row in S.MBW_ROWS}
-    # block tiles: Cout <= 32 gives nRowT = 2, so the six-row-tile variants (MAXRT = 6) cannot be reached through pcv_mbconv_fused
-    blk = {("blk", (s, e, 2)) for s in (1, 2) for e in (True, False)}
-    assert not any(k == "blk" and inst[2] == 6 for k, inst in reached)
+    # block tiles: mbconv_kernel<DT, S, EXPAND> is compiled for two projection row tiles (Cout <= 32) and nothing else, so these four
+    # per dtype are EVERY instance of it
+    blk = {("blk", (s, e)) for s in (1, 2) for e in (True, False)}
+    assert re.search(r"^constexpr int kMbRowT = 2;", _src("mbconv.hpp"), re.M) and "MAXRT" not in _src("mbconv.hpp")
+    assert len(re.findall(r"mbconv_kernel<DT, [12], (?:true|false)>", _src("pcv_api.hip"))) == 4
     missing = (mbr | mbw | blk) - reached
     assert not missing, sorted(missing, key=repr)
     assert reached <= (mbr | mbw | blk)

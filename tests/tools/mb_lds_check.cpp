@@ -4,7 +4,7 @@
 //   mbr nrt nChunks ka afl wel xrows waves | mbw stride nrt nChunks nWaves tw ka rb | mb stride expand ka nChunks nRowT nbufX
 #include <cstdio>
 #include <cstring>
-#include "mbconv.hpp"
+#include "mbconv.hpp"      // (each includes csrc/mb_device.hpp and no sibling: any order, any subset)
 #include "mbw.hpp"
 #include "mbr.hpp"
 

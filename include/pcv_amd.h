@@ -35,7 +35,8 @@ extern "C" {
  * 5: + split attention (pcv_splat_squeeze / _excite / _combine) and padded average pool (pcv_avgpool2d_pad); no layout change
  *    (still 5: + pcv_resize_plan_bytes / pcv_resize_plan / pcv_resize_crop_u8 - pure additions, no signature, struct or blob of
  *    version 5 changes, so a version-5 binding keeps working against this library and the number does not move;
- *    likewise + pcv_classify_f32, + pcv_cbam_pool / _excite / _spatial_pool / _apply) */
+ *    likewise + pcv_classify_f32, + pcv_cbam_pool / _excite / _spatial_pool / _apply,
+ *    + pcv_mixconv_packed_bytes / pcv_mixconv_pack / pcv_mixconv2d_fused) */
 #define PCV_ABI_VERSION 5
 
 typedef struct pcv_ctx pcv_ctx;
@@ -226,6 +227,28 @@ int pcv_conv2d_nchw_stem_fused(pcv_ctx* ctx, const pcv_conv_desc* d, const float
 /* Depthwise direct convolution, fused epilogue (same contract). */
 int pcv_dwconv2d_fused(pcv_ctx* ctx, const pcv_conv_desc* d, const void* x, const void* packed,
                        const float* scale, const float* shift, const void* residual, void* y, void* stream);
+/* Depthwise MixConv as ONE launch: y = act(scale * mixdw(x) + shift). Replaces MixConv.forward with groups == channels
+ * (mixnet.py:76-80: torch.split, one depthwise Conv2d per channel group, torch.cat) + BatchNorm2d(eval) + activation of
+ * MixConvBlock.forward (mixnet.py:151-157), the `conv1` of MixUnit (mixnet.py:256-263). `kernels` is the list 3, 5, ..., 3 + 2 (nk - 1)
+ * with nk = 2 .. 5 (mixnet.py:259); group g takes the channels MixConv.split_channels gives it (mixnet.py:83-86: C // nk each, the
+ * first group the remainder), reads its slice of the dense NHWC x [N,H,W,C] in place and writes its slice of y [N,Ho,Wo,C]: no slice
+ * copy, no concatenation copy, no launch per group. The descriptor is a depthwise one (groups == Cin == Cout, C % 8 == 0) with
+ * kh = kw = the LARGEST window and all four pads = kh / 2 (padding is k // 2 per group, mixnet.py:261: every group has the same output
+ * size); stride 1 or 2; every activation code; fp16 results are range-guarded.
+ * Refused with PCV_ERR_INVALID and a text (pcv_last_error; pcv_last_error(NULL) for pcv_mixconv_packed_bytes), before any device call:
+ * a stale descriptor size, groups != Cin, a kernel list of another form, an ODD group width (only a split such as 40 -> 14, 13, 13
+ * gives one), has_residual / post_act (MixUnit has neither behind conv1), dilation, padded pitches, pads other than kh / 2.
+ *   pcv_mixconv_packed_bytes  size of the packed blob (host arithmetic only)
+ *   pcv_mixconv_pack          w: HOST array of nk DEVICE pointers, w[g] = fp32 [Cg,1,k,k] exactly as `conv.<g>.weight` of the state dict
+ *                             (mixnet.py:63-73) -> packed: per window class the taps [k*k][channels of the class] in dtype; a chunk of
+ *                             channels that straddles a group boundary runs the larger window with the smaller filter zero-embedded
+ *                             at its centre (layout in DESIGN.md). Weight-load time; asynchronous on `stream`, w[g] borrowed until it ran.
+ *   pcv_mixconv2d_fused       the launch: no allocation, no synchronisation (capturable). */
+int pcv_mixconv_packed_bytes(const pcv_conv_desc* d, const int* kernels, int nk, size_t* bytes);
+int pcv_mixconv_pack(pcv_ctx* ctx, const pcv_conv_desc* d, const int* kernels, int nk, const float* const* w, void* packed,
+                     void* stream);
+int pcv_mixconv2d_fused(pcv_ctx* ctx, const pcv_conv_desc* d, const int* kernels, int nk, const void* x, const void* packed,
+                        const float* scale, const float* shift, void* y, void* stream);
 /* nn.MaxPool2d(k, s, p, ceil_mode) of ResInitBlock (resnet.py:255-258, floor) and ShuffleInitBlock (shufflenetv2.py:111-115,
  * ceil_mode=True): -inf padding; with ceil_mode the last window may hang over the bottom / right edge (PyTorch's rule). A NaN
  * in a window gives NaN, as in torch. y is [N, Ho, Wo, C] with PyTorch's output size; an empty one is PCV_ERR_INVALID. */

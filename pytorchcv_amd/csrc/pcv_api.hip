@@ -35,6 +35,10 @@ MBW3_SHAPES(MBW3_DECLARE, PCV_F16)
 MBR_SHAPES(MBR_DECLARE, PCV_BF16)
 MBR_SHAPES(MBR_DECLARE, PCV_F16)
 #include "dwconv.hpp"
+#include "mixconv.hpp"
+MIX_INSTANCES(MIX_DECLARE, PCV_F32)
+MIX_INSTANCES(MIX_DECLARE, PCV_BF16)
+MIX_INSTANCES(MIX_DECLARE, PCV_F16)
 #include "aux_kernels.hpp"
 #include "cbam_kernels.hpp"
 #include "resize_kernel.hpp"
@@ -721,6 +725,12 @@ static MbLds mbconv_plan(int stride, bool expand, int ka, int nChunks, int nRowT
     *nbufX = 2;
     return two;
 }
+
+// depthwise MixConv (mixconv.hpp): [storage type][stride - 1][clamp-only activation][kernels - 2]; no dynamic LDS
+#define MIX_KERNEL(DT, S, FAST, G) kernel_of(mixdw_kernel<DT, S, FAST, G>, 256, 0)
+#define MIX_ROW(DT, S, FAST) {MIX_KERNEL(DT, S, FAST, 2), MIX_KERNEL(DT, S, FAST, 3), MIX_KERNEL(DT, S, FAST, 4), MIX_KERNEL(DT, S, FAST, 5)}
+#define MIX_TYPE(DT) {{MIX_ROW(DT, 1, false), MIX_ROW(DT, 1, true)}, {MIX_ROW(DT, 2, false), MIX_ROW(DT, 2, true)}}
+static const Kernel kMix[3][2][2][4] = {MIX_TYPE(PCV_F32), MIX_TYPE(PCV_BF16), MIX_TYPE(PCV_F16)};
 
 // top-k / softmax / label rank (classify_kernel.hpp): one wave per row up to 1024 entries, four above; LDS = scratch + the row
 static Kernel classify_kernel_of(int J) {
@@ -1780,6 +1790,117 @@ int pcv_dwconv2d_fused(pcv_ctx* ctx, const pcv_conv_desc* d, const void* x, cons
     if (int rc = flat_grid(ctx, "pcv_dwconv2d_fused", p.total, &grid)) return rc;
     launch_dw(*d, p, grid, (hipStream_t)stream);
     return launched(ctx);
+}
+
+// ---- depthwise MixConv (mixconv.hpp) ---------------------------------------------------------------------------------------------
+// every argument check of the three entry points; G = nk on success
+static const char* check_mix(const pcv_conv_desc& d, const int* ks, int nk, MixPlan& P) {
+    if (desc_stale(d)) return kStaleDesc;
+    if (!dtype_ok(d.dtype) || d.out_dtype != d.dtype) return "mixconv: out_dtype must equal dtype";
+    if (d.groups != d.Cin || d.Cin != d.Cout) return "mixconv: needs groups == Cin == Cout (the 1x1 MixConv is pcv_conv2d_fused with groups = 2)";
+    if (!ks || nk < 2 || nk > kMixMaxGroups) return "mixconv: the kernel list must be 3, 5, ..., 3 + 2 (G - 1) with G = 2 .. 5";
+    for (int g = 0; g < nk; ++g)
+        if (ks[g] != 3 + 2 * g) return "mixconv: the kernel list must be 3, 5, ..., 3 + 2 (G - 1) with G = 2 .. 5";
+    if (d.kh != ks[nk - 1] || d.kw != ks[nk - 1]) return "mixconv: kh / kw must be the largest window of the list";
+    if (d.pad_t != d.kh / 2 || d.pad_b != d.kh / 2 || d.pad_l != d.kh / 2 || d.pad_r != d.kh / 2)
+        return "mixconv: padding must be k / 2 of every window (pad fields: that of the largest)";
+    if (d.stride_h != d.stride_w || (d.stride_h != 1 && d.stride_h != 2)) return "mixconv: stride 1 or 2";
+    if (d.dil_h != 1 || d.dil_w != 1) return "mixconv: dilation unsupported";
+    if (d.has_residual || d.post_act != PCV_ACT_NONE) return "mixconv: no residual / post-activation (MixUnit has none behind conv1)";
+    if (d.act < PCV_ACT_NONE || d.act > PCV_ACT_HSWISH) return "mixconv: unknown activation";
+    if (d.x_cpitch > 0 && d.x_cpitch != d.Cin) return "mixconv: padded channel pitch unsupported";
+    if (d.x_wpitch > 0 && d.x_wpitch != d.W) return "mixconv: padded row pitch unsupported";
+    if (d.y_cpitch > 0 && d.y_cpitch != d.Cout) return "mixconv: y must be dense";
+    const char* why = nullptr;
+    if (!mix_plan(d.Cin, nk, esize(d.dtype), P, &why)) return why;
+    return nullptr;
+}
+
+int pcv_mixconv_packed_bytes(const pcv_conv_desc* d, const int* kernels, int nk, size_t* bytes) {
+    MixPlan P;
+    if (!d || !bytes) return fail(nullptr, PCV_ERR_INVALID, "pcv_mixconv_packed_bytes: NULL argument");
+    if (const char* why = check_mix(*d, kernels, nk, P)) return fail(nullptr, PCV_ERR_INVALID, std::string("pcv_mixconv_packed_bytes: ") + why);
+    *bytes = P.bytes;
+    return PCV_OK;
+}
+
+int pcv_mixconv_pack(pcv_ctx* ctx, const pcv_conv_desc* d, const int* kernels, int nk, const float* const* w, void* packed, void* stream) {
+    PCV_ENTER(ctx);
+    if (!d || !w || !packed) return fail(ctx, PCV_ERR_INVALID, "pcv_mixconv_pack: NULL argument");
+    MixPlan P;
+    if (const char* why = check_mix(*d, kernels, nk, P)) return fail(ctx, PCV_ERR_INVALID, std::string("pcv_mixconv_pack: ") + why);
+    if (!aligned16(packed)) return fail(ctx, PCV_ERR_INVALID, "pcv_mixconv_pack: packed buffer must be 16-byte aligned");
+    MixPackParams q = {};
+    q.out = packed;
+    q.G = nk;
+    q.wr = d->Cin / nk;
+    q.w0 = d->Cin - (nk - 1) * q.wr;
+    long long total = 0;
+    for (int g = 0; g < kMixMaxGroups; ++g) {
+        if (g < nk && !w[g]) return fail(ctx, PCV_ERR_INVALID, "pcv_mixconv_pack: NULL weight pointer in the list");
+        q.w[g] = g < nk ? w[g] : nullptr;
+        q.cbeg[g] = P.cbeg[g];
+        q.span[g] = P.span[g];
+        q.woff[g] = P.woff[g];
+        total += (long long)(3 + 2 * g) * (3 + 2 * g) * P.span[g];
+        q.elem_end[g] = (int)total;
+    }
+    if (total >= 0x7fffffffll) return too_large(ctx, "pcv_mixconv_pack", "the blob");
+    unsigned grid = 0;
+    if (int rc = flat_grid(ctx, "pcv_mixconv_pack", total, &grid)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    for_dtype(d->dtype, [&](auto T) { pack_mix_kernel<DT_OF(T)><<<grid, 256, 0, s>>>(q); });
+    return launched(ctx);
+}
+
+int pcv_mixconv2d_fused(pcv_ctx* ctx, const pcv_conv_desc* d, const int* kernels, int nk, const void* x, const void* packed,
+                        const float* scale, const float* shift, void* y, void* stream) {
+    PCV_ENTER(ctx);
+    if (!d || !x || !packed || !y || !scale || !shift) return fail(ctx, PCV_ERR_INVALID, "pcv_mixconv2d_fused: NULL argument");
+    MixPlan P;
+    if (const char* why = check_mix(*d, kernels, nk, P)) return fail(ctx, PCV_ERR_INVALID, std::string("pcv_mixconv2d_fused: ") + why);
+    if (d->N <= 0 || d->H <= 0 || d->W <= 0) return fail(ctx, PCV_ERR_INVALID, "pcv_mixconv2d_fused: empty input");
+    if (!aligned16(x) || !aligned16(packed) || !aligned16(y) || !aligned16(scale) || !aligned16(shift))
+        return fail(ctx, PCV_ERR_INVALID, "pcv_mixconv2d_fused: pointers must be 16-byte aligned");
+    MixParams p = {};
+    p.x = x;
+    p.w = packed;
+    p.y = y;
+    p.scale = scale;
+    p.shift = shift;
+    p.ovf = ctx->ovf;
+    p.N = d->N; p.H = d->H; p.W = d->W; p.C = d->Cin;
+    const unsigned long long xbytes = (unsigned long long)d->N * d->H * d->W * d->Cin * esize(d->dtype);
+    if (!in_window(xbytes)) return too_large(ctx, "pcv_mixconv2d_fused", "input");
+    p.x_bytes = (uint32_t)xbytes;
+    p.Ho = (d->H - 1) / d->stride_h + 1;           // pad k / 2 on both sides: the same for every window of the list
+    p.Wo = (d->W - 1) / d->stride_w + 1;
+    // rows per thread as pcv_dwconv2d_fused chooses them, from the columns of 4-channel chunks
+    const long cols = (long)d->N * p.Wo * (d->Cin / 4);
+    const long want = (long)ctx->num_cu * 64 * 16;
+    int nseg = (int)((want + cols - 1) / cols);
+    if (nseg < 1) nseg = 1;
+    int TH = (p.Ho + nseg - 1) / nseg;
+    if (TH < 4) TH = p.Ho < 4 ? p.Ho : 4;
+    if (ctx->dw_th > 0) TH = ctx->dw_th < p.Ho ? ctx->dw_th : p.Ho;
+    p.TH = TH;
+    p.nseg = (p.Ho + TH - 1) / TH;
+    p.act = d->act;
+    p.flags = ctx->dw_flags;
+    long long blocks = 0;
+    for (int g = 0; g < kMixMaxGroups; ++g) {
+        p.cbeg[g] = P.cbeg[g];
+        p.span[g] = P.span[g];
+        p.nchunk[g] = P.span[g] / P.cpt[g];
+        p.woff[g] = P.woff[g];
+        unsigned nb = 0;
+        if (int rc = flat_grid(ctx, "pcv_mixconv2d_fused", (long long)d->N * p.nseg * p.Wo * p.nchunk[g], &nb)) return rc;
+        blocks += nb;
+        if (blocks > 0x7fffffffll) return too_large(ctx, "pcv_mixconv2d_fused", "the grid");
+        p.blk_end[g] = (uint32_t)blocks;
+    }
+    const Kernel& K = kMix[d->dtype == PCV_F32 ? 0 : (d->dtype == PCV_BF16 ? 1 : 2)][d->stride_h - 1][d->act <= PCV_ACT_RELU6 ? 1 : 0][nk - 2];
+    return launch(ctx, K, (unsigned)blocks, (hipStream_t)stream, p);
 }
 
 static int pool_out(int in, int k, int s, int p, int ceil_mode) {

@@ -5,7 +5,7 @@
 """
 
 __all__ = ['NHWC', 'DTYPES', 'default_dtype', 'set_compute_dtype', 'compute_dtype_of', 'Fp16Guard', 'fp16_overflow_count', 'from_nchw', 'to_nchw', 'ConvRunner',
-           'BnActRunner', 'maxpool2d', 'avgpool2d', 'avgpool2d_pad', 'global_avgpool', 'se_excite', 'se_scale', 'se_forward', 'splat_forward', 'cbam_channel_gate', 'cbam_spatial', 'cbam_forward', 'channel_slice', 'cat_shuffle2', 'act_code',
+           'MixConvRunner', 'BnActRunner', 'maxpool2d', 'avgpool2d', 'avgpool2d_pad', 'global_avgpool', 'se_excite', 'se_scale', 'se_forward', 'splat_forward', 'cbam_channel_gate', 'cbam_spatial', 'cbam_forward', 'channel_slice', 'cat_shuffle2', 'act_code',
            'boundary', 'round8', 'channel_concat_into', 'interpolate', 'add', 'classify']
 
 import os
@@ -598,6 +598,108 @@ class ConvRunner(object):
         _call(z.device, "fc_f32", _ptr(mean), _ptr(self._sq_w1), _ptr(self._sq_b1), _ptr(mid), z.N, d.Cin, M, mid_act)
         _call(z.device, "fc_f32", _ptr(mid), _ptr(self._sq_w2), _ptr(self._sq_b2), _ptr(gate), z.N, M, d.Cout, out_act)
         return gate
+
+
+class MixConvRunner(ConvRunner):
+    """
+    Packed state of one depthwise MixConv (+ BatchNorm2d): the G depthwise Conv2d modules of a reference MixConv (mixnet.py:59-73,
+    windows 3, 5, ..., 3 + 2 (G - 1), padding k // 2) as ONE blob (pcv_mixconv_pack) and the folded fp32 scale / shift of the block's
+    BatchNorm over all channels. One launch per block (pcv_mixconv2d_fused): every group reads and writes its channel slice in place.
+    A ConvRunner as far as the packed-state plumbing goes (cache key, parallel.broadcast_packed_state).
+    """
+    def __init__(self, convs, bn):
+        self.convs = list(convs)
+        self.conv, self.bn, self.pad4 = self.convs[0], bn, None
+        self._key = None
+        self._foreign = False
+        self.packed = self.scale = self.shift = None
+        self.depthwise = True
+        G = len(self.convs)
+        for g, c in enumerate(self.convs):
+            k = 3 + 2 * g
+            if _pair(c.kernel_size) != (k, k) or _pair(c.padding) != (k // 2, k // 2) or _pair(c.dilation) != (1, 1) or \
+                    c.groups != c.in_channels or c.in_channels != c.out_channels or _pair(c.stride) != _pair(self.conv.stride) or \
+                    c.padding_mode != "zeros":
+                raise NotImplementedError("MixConv on the MI355X path: depthwise groups with windows 3, 5, ... and padding k // 2, "
+                                          "got group {} = {}".format(g, c))
+        if not 2 <= G <= 5:
+            raise NotImplementedError("MixConv with {} kernels: the MI355X path takes 2 to 5".format(G))
+        self.channels = sum(c.out_channels for c in self.convs)
+        self.kernels = (ctypes.c_int * G)(*[3 + 2 * g for g in range(G)])
+
+    def _sources(self):
+        ts = []
+        for c in self.convs:
+            ts += [c.weight, c.bias]
+        if self.bn is not None:
+            ts += [self.bn.weight, self.bn.bias, self.bn.running_mean, self.bn.running_var]
+        return ts
+
+    def desc(self, x: NHWC, act: int) -> ConvDesc:
+        C, G = self.channels, len(self.convs)
+        if not x.dense or x.C != C or x.cpitch != C:
+            raise RuntimeError("MixConv expects a dense handle of {} channels (a multiple of 8), got {} / pitch {}".format(C, x.C, x.cpitch))
+        k = 3 + 2 * (G - 1)
+        s = _pair(self.conv.stride)
+        code = _CODE_OF_TORCH[x.dtype]
+        return ConvDesc(N=x.N, H=x.H, W=x.W, Cin=C, Cout=C, kh=k, kw=k, stride_h=s[0], stride_w=s[1], pad_t=k // 2, pad_l=k // 2,
+                        pad_b=k // 2, pad_r=k // 2, dil_h=1, dil_w=1, groups=C, act=act, post_act=0, has_residual=0, dtype=code,
+                        out_dtype=code, x_cpitch=C, x_wpitch=x.W)
+
+    def prepare(self, x: NHWC, d: ConvDesc):
+        key = (x.dtype, d.Cin) + tuple((t.data_ptr(), t._version) if t is not None else None for t in self._sources())
+        if key == self._key:
+            return
+        if self._foreign:
+            raise RuntimeError("this MixConv's packed weights were received by parallel.broadcast_packed_state and would have to be "
+                               "re-packed: call parallel.broadcast_module_state(net) first")
+        dev, C, G = x.device, d.Cin, len(self.convs)
+        if self.conv.weight.device != dev:
+            raise RuntimeError("model parameters are on {} but the input is on {}".format(self.conv.weight.device, dev))
+        L = _lib.lib()
+        nbytes = ctypes.c_size_t(0)
+        if L.pcv_mixconv_packed_bytes(ctypes.byref(d), self.kernels, G, ctypes.byref(nbytes)) != 0:
+            raise _lib.PcvError(-1, "unsupported MixConv configuration: {}".format((L.pcv_last_error(None) or b"").decode()))
+        packed = torch.empty((nbytes.value + 15) // 16 * 16, dtype=torch.uint8, device=dev)
+        ws = [c.weight.detach().float().contiguous() for c in self.convs]
+        _call(dev, "mixconv_pack", ctypes.byref(d), self.kernels, G, (ctypes.c_void_p * G)(*[w.data_ptr() for w in ws]), _ptr(packed))
+        scale = torch.empty(C, dtype=torch.float32, device=dev)
+        shift = torch.empty(C, dtype=torch.float32, device=dev)
+        bias = None
+        if any(c.bias is not None for c in self.convs):
+            bias = torch.cat([c.bias.detach().float() if c.bias is not None else torch.zeros(c.out_channels, device=dev)
+                              for c in self.convs]).contiguous()
+        bn = self.bn
+        if bn is not None:
+            if not isinstance(bn, nn.BatchNorm2d):
+                raise NotImplementedError("only BatchNorm2d folds into the conv epilogue, got {}".format(type(bn).__name__))
+            g = (bn.weight if bn.weight is not None else torch.ones(C, device=dev)).detach().float().contiguous()
+            b = (bn.bias if bn.bias is not None else torch.zeros(C, device=dev)).detach().float().contiguous()
+            m, v = bn.running_mean.detach().float().contiguous(), bn.running_var.detach().float().contiguous()
+            _call(dev, "bn_fold", C, _ptr(g), _ptr(b), _ptr(m), _ptr(v), ctypes.c_float(bn.eps), _ptr(bias), _ptr(scale), _ptr(shift))
+        else:
+            _call(dev, "bn_fold", C, None, None, None, None, ctypes.c_float(0.0), _ptr(bias), _ptr(scale), _ptr(shift))
+        torch.cuda.current_stream(dev).synchronize()      # the fp32 copies are temporaries; load-time only
+        self.packed, self.scale, self.shift, self._key = packed, scale, shift, key
+
+    def run(self, x: NHWC, act: int = 0) -> NHWC:
+        _require_eval(self)
+        d = self.desc(x, act)
+        self.prepare(x, d)
+        Ho, Wo = _conv_out(d, x.H, x.W)
+        y = torch.empty((x.N, Ho, Wo, d.Cout), dtype=x.dtype, device=x.device)
+        self._launch_range(x, d, None, y, 0, x.N)
+        return NHWC(y, x.N, Ho, Wo, self.channels, cpitch=d.Cout)
+
+    def _launch_range(self, x, d, residual, y, n0, n1, gate=None):
+        """Launch images [n0, n1); halve the range when one launch would exceed the 2 GiB addressing window."""
+        d.N = n1 - n0
+        rc = _call(x.device, "mixconv2d_fused", ctypes.byref(d), self.kernels, len(self.convs), _ptr(x.t[n0:n1]), _ptr(self.packed),
+                   _ptr(self.scale), _ptr(self.shift), _ptr(y[n0:n1]), accept=(_lib.PCV_ERR_TOO_LARGE,) if n1 - n0 > 1 else ())
+        if rc != 0:
+            mid = (n0 + n1) // 2
+            self._launch_range(x, d, None, y, n0, mid)
+            self._launch_range(x, d, None, y, mid, n1)
 
 
 def _pool_out(n: int, k: int, s: int, p: int, ceil_mode: bool) -> int:

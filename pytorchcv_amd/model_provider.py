@@ -2,7 +2,7 @@
     `get_model(name, **kwargs)` with the reference's contract (pytorchcv/model_provider.py:1364-1382): case-insensitive
     name, `ValueError("Unsupported model: ...")` for unknown names, kwargs (`pretrained`, `root`, `in_channels`, `in_size`,
     `num_classes`) forwarded to the factory. The registry holds the families whose whole forward runs on the MI355X hot
-    path (ResNet, SE-ResNet, ResNeXt, SE-ResNeXt, MobileNet, MobileNetV2, MobileNetV3, EfficientNet, PreResNet, SE-PreResNet, DenseNet, ShuffleNetV2, VGG, ResNeSt(A), SKNet, CBAM-ResNet).
+    path (ResNet, SE-ResNet, ResNeXt, SE-ResNeXt, MobileNet, MobileNetV2, MobileNetV3, EfficientNet, PreResNet, SE-PreResNet, DenseNet, ShuffleNetV2, VGG, ResNeSt(A), SKNet, CBAM-ResNet, MixNet).
 """
 
 __all__ = ['get_model']
@@ -23,6 +23,7 @@ from .models import vgg as _vgg
 from .models import resnesta as _resnesta
 from .models import sknet as _sknet
 from .models import cbamresnet as _cbamresnet
+from .models import mixnet as _mixnet
 
 _models = {}
 for _mod in (_resnet, _mobilenetv2, _resnext, _seresnet, _seresnext, _mobilenet, _mobilenetv3, _efficientnet, _preresnet, _sepreresnet, _densenet, _shufflenetv2, _vgg, _resnesta, _sknet):
@@ -35,11 +36,13 @@ for _mod in (_resnet, _mobilenetv2, _resnext, _seresnet, _seresnext, _mobilenet,
 # `_models`, and a family that arrives with end-to-end tests of its own (CBAM-ResNet) is registered here so that those keep
 # covering exactly the nets they were written for. `get_model` does not tell the two apart.
 _models_cbam = {_name: getattr(_cbamresnet, _name) for _name in _cbamresnet.__all__ if _name.startswith("cbam_resnet")}
+# ... and a third, on the same grounds: MixNet-S/M/L (mixed-window depthwise convolutions, tests/test_gpu_mixnet.py)
+_models_mixnet = {_name: getattr(_mixnet, _name) for _name in ("mixnet_s", "mixnet_m", "mixnet_l")}
 
 
 def get_model(name, **kwargs):
     name = name.lower()
-    fn = _models.get(name) or _models_cbam.get(name)
+    fn = _models.get(name) or _models_cbam.get(name) or _models_mixnet.get(name)
     if fn is None:
         raise ValueError("Unsupported model: {}".format(name))
     net = fn(**kwargs)

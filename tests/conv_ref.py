@@ -21,6 +21,11 @@ fp32; the + 3 covers an fp32 product rounding (fp32 storage), the scale multiply
     residual  e_r = e_g + u (|a g| + |res|)
     post_act  e_y = L_post e_r + T_post(r)
     output    |y - ref| <= U |ref| + (1 + U) e_y + F
+A residual the kernel computes itself (res_err, tests/pair_ref.py: the identity convolution recomputed inside the fused 1x1 pair): the
+reference adds the exact float64 skip `res`, the kernel adds a value res' with |res' - res| <= res_err elementwise. The sum a g + res'
+is off by e_g + res_err before the addition rounds, and the addition rounds a result of magnitude at most |a g| + |res| + res_err:
+    residual  e_r = e_g + res_err + u (|a g| + |res| + res_err)
+With res_err = None (a residual read from memory, exact) this is the line above.
 Pooled stem (the MaxPool2d(3, 2, 1) fused behind the convolution): the reference is the pool, with -inf padding, of the reference
 ROUNDED to the storage type. max is 1-Lipschitz in the maximum norm, so the pooled bound is the maximum over the window of the
 per-element distance to that rounded reference: the per-element bound above plus the U |ref| by which the rounding moved the
@@ -81,8 +86,9 @@ def conv_terms(x, w, g):
     return z, S
 
 
-def conv_ref_err(x, w, scale, shift, geom, act, res=None, post=NONE, gate=None):
-    """(reference, S, bound of the kernel's fp32 error before the output rounding), all float64 NHWC [N][Ho][Wo][Cout]"""
+def conv_ref_err(x, w, scale, shift, geom, act, res=None, post=NONE, gate=None, res_err=None):
+    """(reference, S, bound of the kernel's fp32 error before the output rounding), all float64 NHWC [N][Ho][Wo][Cout]; res_err: an
+    elementwise bound on the error of a residual the kernel computes itself (module docstring), None for one it reads"""
     z, S = conv_terms(x, w, geom)
     K = geom.kh * geom.kw * (geom.Cin // geom.groups)
     sc = scale.double() if scale is not None else torch.ones(z.shape[-1], dtype=torch.float64)
@@ -98,7 +104,10 @@ def conv_ref_err(x, w, scale, shift, geom, act, res=None, post=NONE, gate=None):
     v = a
     if res is not None:
         v = a + res.double()
-        err = err + U32 * (a.abs() + res.double().abs())
+        if res_err is None:
+            err = err + U32 * (a.abs() + res.double().abs())
+        else:
+            err = err + res_err + U32 * (a.abs() + res.double().abs() + res_err)
     y = act64(v, post)
     if post != NONE:
         err = act_err(v, err, post)
@@ -111,9 +120,9 @@ def conv_ref(x, w, scale, shift, geom, act, res=None, post=NONE, gate=None):
     return y, S
 
 
-def conv_ref_bound(x, w, scale, shift, geom, act, res=None, post=NONE, gate=None, out_dtype="fp32"):
+def conv_ref_bound(x, w, scale, shift, geom, act, res=None, post=NONE, gate=None, out_dtype="fp32", res_err=None):
     """(reference, elementwise bound on |y - reference| for a y stored as out_dtype)"""
-    y, _, err = conv_ref_err(x, w, scale, shift, geom, act, res, post, gate)
+    y, _, err = conv_ref_err(x, w, scale, shift, geom, act, res, post, gate, res_err)
     return y, out_bound(y, err, out_dtype)
 
 

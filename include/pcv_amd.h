@@ -36,7 +36,7 @@ extern "C" {
  *    (still 5: + pcv_resize_plan_bytes / pcv_resize_plan / pcv_resize_crop_u8 - pure additions, no signature, struct or blob of
  *    version 5 changes, so a version-5 binding keeps working against this library and the number does not move;
  *    likewise + pcv_classify_f32, + pcv_cbam_pool / _excite / _spatial_pool / _apply,
- *    + pcv_mixconv_packed_bytes / pcv_mixconv_pack / pcv_mixconv2d_fused) */
+ *    + pcv_mixconv_packed_bytes / pcv_mixconv_pack / pcv_mixconv2d_fused, + pcv_bottleneck_supported / pcv_bottleneck_fused) */
 #define PCV_ABI_VERSION 5
 
 typedef struct pcv_ctx pcv_ctx;
@@ -365,6 +365,23 @@ int pcv_conv1x1_pair_idconv_fused(pcv_ctx* ctx, const pcv_conv_desc* d_id, const
                                   const void* x0, const void* packed_id, const float* scale_id, const float* shift_id,
                                   const void* x, const void* packed1, const float* scale1, const float* shift1, void* y1,
                                   const void* packed2, const float* scale2, const float* shift2, void* y2, void* stream);
+
+/* A whole bottleneck unit of ResNet's 56 x 56 stage in one launch: y = post_act(act3(BN(conv3(t2))) + skip) with
+ * t2 = act2(BN(conv2(t1))), t1 = act1(BN(conv1(x))) - ResBottleneck.forward (resnet.py:136-140) and the `x + identity` + ReLU of
+ * ResUnit.forward (resnet.py:221-229). skip = x (d_id == NULL; 256 -> 64 -> 64 -> 256) or BN(conv_id(x)) (d_id, packed_id, scale_id,
+ * shift_id: the unit's `identity_conv`, resnet.py:214-216; 64 -> 64 -> 64 -> 256). t1 and t2 stay on the CU: x is read once, y written
+ * once. The descriptors and packed blobs are those of the separate pcv_conv2d_fused calls; d3 carries has_residual and post_act.
+ * t1, t2, the identity convolution's result and y are rounded to the storage type exactly where the separate launches store them; the
+ * value of an output element does not depend on the batch size, on its position in the batch or on how the launch splits the images.
+ * `pcv_bottleneck_supported`: 16-bit storage, 56-wide maps, conv2 3x3 / stride 1 / pad 1, those channel counts, activations none /
+ * ReLU / ReLU6, the output below 2 GiB - decided by shapes and dtype alone; pcv_set_tuning(ctx, "bnu", 0) switches it off for the
+ * process. Anything else is run as the separate calls. */
+int pcv_bottleneck_supported(const pcv_conv_desc* d1, const pcv_conv_desc* d2, const pcv_conv_desc* d3, const pcv_conv_desc* d_id);
+int pcv_bottleneck_fused(pcv_ctx* ctx, const pcv_conv_desc* d1, const pcv_conv_desc* d2, const pcv_conv_desc* d3,
+                         const pcv_conv_desc* d_id, const void* x, const void* packed1, const float* scale1, const float* shift1,
+                         const void* packed2, const float* scale2, const float* shift2, const void* packed3, const float* scale3,
+                         const float* shift3, const void* packed_id, const float* scale_id, const float* shift_id, void* y,
+                         void* stream);
 
 /* A whole inverted-residual unit in one launch: [1x1 expand ConvBlock] -> depthwise 3x3 ConvBlock -> 1x1 project ConvBlock
  * (+ skip add): LinearBottleneck.forward (mobilenetv2.py:62-71), MobileNetV3Unit without SE (mobilenetv3.py:82-93),

@@ -21,6 +21,7 @@
 #include "stem_conv.hpp"
 #include "pair1x1.hpp"
 #include "wpair1x1.hpp"
+#include "bnu.hpp"
 #include "gconv3x3.hpp"
 #include "gconv3x3r.hpp"
 #include "mbconv.hpp"
@@ -75,6 +76,11 @@ extern template __global__ void d1i_kernel<PCV_F16, 2048>(const D3Params);
 P1R_DECLARE(64, 256)
 P1R_DECLARE(32, 512)
 P1R_DECLARE(32, 256)
+#define BNU_DECLARE(DT)                                                          \
+    extern template __global__ void bnu_kernel<DT, false>(const BnuParams);      \
+    extern template __global__ void bnu_kernel<DT, true>(const BnuParams);
+BNU_DECLARE(PCV_BF16)
+BNU_DECLARE(PCV_F16)
 
 enum TileCfg { TILE_C32 = 0, TILE_C64 = 1, TILE_C128 = 2, TILE_C256 = 3, TILE_C64S = 4, TILE_C128S = 5, TILE_COUNT = 6 };
 
@@ -106,6 +112,7 @@ struct pcv_ctx {
     int dw_th = 0;              // tuning: rows per thread of the depthwise kernel (0 = automatic)
     int max_blocks = 0;         // test-only: cap on every persistent grid (0 = resident blocks), so that small fixtures walk several
                                 // tiles per block through the cross-tile pipelines (pcv_set_tuning("max_blocks", n))
+    int bnu_band = 0;           // fused stage-1 bottleneck unit (bnu.hpp): rows per band, 0 = whole images once they fill the chip, else bands of >= 4 rows (tests: any value)
     int pair_pb = 2;            // fused 1x1 pair: 16-pixel blocks per tile (2: two blocks per CU, 4: one 512-register block)
     int persist_max_nk = 4;     // auto: persistent when a tile has at most this many K-steps (PCV_AMD_PERSIST_NK)
     uint32_t* ovf = nullptr;    // device word: how many threads have rounded a value beyond fp16's range so far (F16Guard, pcv_common.hpp);
@@ -613,6 +620,10 @@ enum PairForm { PAIR_PB4 = 0, PAIR_PB2 = 1, PAIR_GATED = 2, PAIR_IDCONV = 3 };  
     {kernel_of(pair1x1_kernel<DT, 4>, 256, pair_lds(4)), kernel_of(pair1x1_kernel<DT, 2>, 256, pair_lds(2)),                  \
      kernel_of(pair1x1_kernel<DT, 2, false, true>, 256, pair_lds(2)), kernel_of(pair1x1_kernel<DT, 2, true>, 256, pair_lds(2, true))}
 static const Kernel kPair[2][4] = {PAIR_ROW(PCV_BF16), PAIR_ROW(PCV_F16)};      // [bf16, fp16][PairForm]
+// fused stage-1 bottleneck unit (bnu.hpp): [bf16, fp16][plain, identity-convolution form]; one 8-wave block per CU
+#define BNU_ROW(DT) {kernel_of(bnu_kernel<DT, false>, 512, BnuCfg<false>::LDS), kernel_of(bnu_kernel<DT, true>, 512, BnuCfg<true>::LDS)}
+static const Kernel kBnu[2][2] = {BNU_ROW(PCV_BF16), BNU_ROW(PCV_F16)};
+static int g_bnu = -1;                  // "bnu": -1 = the fused unit where supported, 0 = never (process-wide: read by pcv_bottleneck_supported, which has no context)
 // The two switches that stay process-wide: the context-free *_supported predicates of the ABI read them (pcv_set_tuning writes them
 // through any context, for every context).
 static int g_wpair_mask = 3;            // "wpair": bit 0: CM = 128, bit 1: CM = 256
@@ -787,6 +798,8 @@ static int enable_kernels(pcv_ctx* ctx) {
         on(kPair[0][form]);
         on(kPair[1][form], form == PAIR_GATED ? nullptr : form == PAIR_IDCONV ? &ctx->pair_idc_bpc : &ctx->pair_bpc[form]);
     }
+    for (int t = 0; t < 2; ++t)
+        for (int form = 0; form < 2; ++form) on(kBnu[t][form]);
     for (int cfg = 0; cfg < 4; ++cfg)
         for (int gated = 0; gated < 2; ++gated) {
             on(wpair_launch(cfg, PCV_BF16, gated != 0).k);
@@ -943,7 +956,7 @@ static const struct { const char* key; int pcv_ctx::*field; } kTuningKeys[] = {
     {"head", &pcv_ctx::use_head},        {"stem32", &pcv_ctx::use_stem32},         {"d1x1", &pcv_ctx::use_d1x1},
     {"gconvr", &pcv_ctx::use_gconvr},    {"mbw", &pcv_ctx::use_mbw},               {"mbr", &pcv_ctx::use_mbr},
     {"mbr_xl", &pcv_ctx::use_mbr_xl},    {"dw_th", &pcv_ctx::dw_th},               {"dw_flags", &pcv_ctx::dw_flags},
-    {"wstat", &pcv_ctx::use_wstat},
+    {"wstat", &pcv_ctx::use_wstat},      {"bnu_band", &pcv_ctx::bnu_band},
 };
 int pcv_set_tuning(pcv_ctx* ctx, const char* key, int value) {
     if (!ctx || !key) return PCV_ERR_INVALID;
@@ -953,8 +966,9 @@ int pcv_set_tuning(pcv_ctx* ctx, const char* key, int value) {
             ctx->*t.field = value;
             return PCV_OK;
         }
-    if (k == "mbw_wide") g_mbw_wide = value;                // these two: process-wide (see their definition)
+    if (k == "mbw_wide") g_mbw_wide = value;                // these three: process-wide (see their definition)
     else if (k == "wpair") g_wpair_mask = value;
+    else if (k == "bnu") g_bnu = value;
     else if (k == "dbg") {
 #ifdef PCV_DBG_FLAGS
         ctx->dbg_flags = value;
@@ -2275,6 +2289,91 @@ int pcv_conv1x1_pair_idconv_fused(pcv_ctx* ctx, const pcv_conv_desc* d_id, const
     p.act1 = d1->act; p.post1 = d1->post_act; p.act2 = d2->act;
     const unsigned grid = (unsigned)std::min<long>(p.nTiles, (long)block_slots(ctx, ctx->pair_idc_bpc));
     return launch(ctx, kPair[d1->dtype == PCV_BF16 ? 0 : 1][PAIR_IDCONV], grid, (hipStream_t)stream, p);
+}
+
+// Which bottleneck units the fused kernel (bnu.hpp) covers: 16 bit, 56-wide maps, 1x1 (256 | 64 with an identity convolution) -> 64,
+// 3x3 / s1 / p1 64 -> 64, 1x1 64 -> 256 with the skip add; clamp activations only. Shape and dtype decide, never the batch size.
+static const char* bottleneck_unsupported(const pcv_conv_desc& a, const pcv_conv_desc& b, const pcv_conv_desc& c, const pcv_conv_desc* di) {
+    if (desc_stale(a) || desc_stale(b) || desc_stale(c) || (di && desc_stale(*di))) return kStaleDesc;
+    if (g_bnu == 0) return "switched off (pcv_set_tuning(\"bnu\", 0))";
+    if (a.dtype != PCV_BF16 && a.dtype != PCV_F16) return "16-bit storage only";
+    if (b.dtype != a.dtype || c.dtype != a.dtype || (di && di->dtype != a.dtype)) return "one storage type for the whole unit";
+    if (!plain_1x1(a) || !plain_1x1(c) || (di && !plain_1x1(*di))) return "conv1, conv3 and the identity convolution must be plain 1x1 stride 1";
+    const bool b3x3 = b.kh == 3 && b.kw == 3 && b.stride_h == 1 && b.stride_w == 1 && b.dil_h == 1 && b.dil_w == 1 && b.pad_t == 1 &&
+                      b.pad_l == 1 && b.pad_b == 1 && b.pad_r == 1 && b.groups == 1 && b.out_dtype == b.dtype &&
+                      (b.x_cpitch == 0 || b.x_cpitch == b.Cin) && (b.x_wpitch == 0 || b.x_wpitch == b.W) && (b.y_cpitch == 0 || b.y_cpitch == b.Cout);
+    if (!b3x3) return "conv2 must be a dense 3x3, stride 1, pad 1";
+    if (a.Cin != (di ? 64 : 256) || a.Cout != 64 || b.Cin != 64 || b.Cout != 64 || c.Cin != 64 || c.Cout != 256)
+        return "only 256 -> 64 -> 64 -> 256 (64 -> .. with an identity convolution) is instantiated";
+    if (a.W != BnuCfg<false>::W || a.N < 1 || a.H < 1) return "56-wide maps only";
+    if (b.N != a.N || b.H != a.H || b.W != a.W || c.N != a.N || c.H != a.H || c.W != a.W) return "shapes do not chain";
+    if (a.has_residual || a.post_act != PCV_ACT_NONE || b.has_residual || b.post_act != PCV_ACT_NONE || !c.has_residual)
+        return "conv3 carries the skip add, conv1 and conv2 do not";
+    if (a.act > PCV_ACT_RELU6 || b.act > PCV_ACT_RELU6 || c.act > PCV_ACT_RELU6 || c.post_act > PCV_ACT_RELU6 || a.act < 0 || b.act < 0 ||
+        c.act < 0 || c.post_act < 0)
+        return "clamp activations only (none / ReLU / ReLU6)";
+    if (di) {
+        if (di->N != a.N || di->H != a.H || di->W != a.W || di->Cin != 64 || di->Cout != 256) return "identity convolution shapes do not match";
+        if (di->act != PCV_ACT_NONE || di->has_residual || di->post_act != PCV_ACT_NONE) return "identity convolution must have no activation";
+    }
+    if ((long)a.N * a.H * a.W * c.Cout * 2 >= (1L << 31)) return kTensorTooLarge;
+    return nullptr;
+}
+
+int pcv_bottleneck_supported(const pcv_conv_desc* d1, const pcv_conv_desc* d2, const pcv_conv_desc* d3, const pcv_conv_desc* d_id) {
+    return (d1 && d2 && d3 && bottleneck_unsupported(*d1, *d2, *d3, d_id) == nullptr) ? 1 : 0;
+}
+
+int pcv_bottleneck_fused(pcv_ctx* ctx, const pcv_conv_desc* d1, const pcv_conv_desc* d2, const pcv_conv_desc* d3, const pcv_conv_desc* d_id,
+                         const void* x, const void* packed1, const float* scale1, const float* shift1, const void* packed2,
+                         const float* scale2, const float* shift2, const void* packed3, const float* scale3, const float* shift3,
+                         const void* packed_id, const float* scale_id, const float* shift_id, void* y, void* stream) {
+    PCV_ENTER(ctx);
+    if (!d1 || !d2 || !d3 || !x || !packed1 || !scale1 || !shift1 || !packed2 || !scale2 || !shift2 || !packed3 || !scale3 || !shift3 || !y ||
+        (d_id && (!packed_id || !scale_id || !shift_id)))
+        return fail(ctx, PCV_ERR_INVALID, "pcv_bottleneck_fused: NULL argument");
+    if (const char* why = bottleneck_unsupported(*d1, *d2, *d3, d_id)) return fail(ctx, PCV_ERR_INVALID, std::string("pcv_bottleneck_fused: ") + why);
+    if (!aligned16(x) || !aligned16(packed1) || !aligned16(packed2) || !aligned16(packed3) || !aligned16(y) || (d_id && !aligned16(packed_id)))
+        return fail(ctx, PCV_ERR_INVALID, "pcv_bottleneck_fused: pointers must be 16-byte aligned");
+    ConvPlan P1, P2, P3, Pi;
+    const char* why = plan_conv(*d1, P1, false);
+    if (!why) why = plan_conv(*d2, P2, false);
+    if (!why) why = plan_conv(*d3, P3, false);
+    if (!why && d_id) why = plan_conv(*d_id, Pi, false);
+    if (why) return fail(ctx, PCV_ERR_INVALID, std::string("pcv_bottleneck_fused: ") + why);
+    if (P1.wrows != 64 || P1.Kpad != d1->Cin || !P2.conv3 || P2.wrows != 64 || P2.Kpad != 9 * 64 || P3.wrows != 256 || P3.Kpad != 64 ||
+        P1.ngb != 1 || P2.ngb != 1 || P3.ngb != 1 || (d_id && (Pi.wrows != 256 || Pi.Kpad != 64 || Pi.ngb != 1)))
+        return fail(ctx, PCV_ERR_INVALID, "pcv_bottleneck_fused: unexpected packed layout");
+    BnuParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.x = x; p.y = y; p.ovf = ctx->ovf;
+    p.w1 = static_cast<const char*>(packed1) + P1.ktab_bytes;
+    p.w2 = static_cast<const char*>(packed2) + P2.ktab_bytes;
+    p.w3 = static_cast<const char*>(packed3) + P3.ktab_bytes;
+    p.scale1 = scale1; p.shift1 = shift1; p.scale2 = scale2; p.shift2 = shift2; p.scale3 = scale3; p.shift3 = shift3;
+    p.w1_bytes = (uint32_t)(64 * d1->Cin * 2); p.w2_bytes = 64 * 9 * 64 * 2; p.w3_bytes = 256 * 64 * 2;
+    if (d_id) {
+        p.wid = static_cast<const char*>(packed_id) + Pi.ktab_bytes;
+        p.wid_bytes = 256 * 64 * 2;
+        p.scale_id = scale_id; p.shift_id = shift_id;
+    }
+    p.N = d1->N; p.H = d1->H;
+    p.y_bytes = (uint32_t)((long)d1->N * d1->H * d1->W * 256 * 2);
+    // Items = (image, band of rows): whole images once they fill the chip, else bands of at least 4 rows (each band recomputes conv1 on
+    // its two halo rows). The split changes which block computes a row, never the row's value.
+    int band = d1->H;
+    if (ctx->bnu_band > 0) band = std::min(ctx->bnu_band, d1->H);
+    else if (d1->N < ctx->num_cu) {
+        const int nb = std::max(1, std::min((d1->H + 3) / 4, (ctx->num_cu + d1->N - 1) / d1->N));
+        band = (d1->H + nb - 1) / nb;
+    }
+    p.band = band; p.nBands = (d1->H + band - 1) / band;
+    const long long items = (long long)d1->N * p.nBands;
+    if (items >= 0x7FFFFFFFll) return fail(ctx, PCV_ERR_TOO_LARGE, "pcv_bottleneck_fused: too many items; split the batch");
+    p.nItems = (int)items;
+    p.act1 = d1->act; p.act2 = d2->act; p.act3 = d3->act; p.post3 = d3->post_act;
+    const unsigned grid = (unsigned)std::min<long long>(items, block_slots(ctx, 1));
+    return launch(ctx, kBnu[d1->dtype == PCV_BF16 ? 0 : 1][d_id ? 1 : 0], grid, (hipStream_t)stream, p);
 }
 
 int pcv_channel_slice(pcv_ctx* ctx, const void* x, void* y, long rows, int C, int offset, int x_cpitch, int y_cpitch, int dtype,

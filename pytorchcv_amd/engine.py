@@ -135,6 +135,9 @@ class _ShapeOnly(object):
         self.N, self.H, self.W, self.C, self.dtype, self.wpitch, self.cpitch = N, H, W, C, dtype, W, round8(C)
 
 
+ShapeOnly = _ShapeOnly      # (public name: a model asks whether a unit WOULD be covered before its input exists - bottleneck_fused's probe)
+
+
 def _device_index(device) -> int:
     if device.type != "cuda":
         raise RuntimeError("pytorchcv_amd runs on MI355X (gfx950) only: got a tensor on '{}'. Move the model and the input "
@@ -848,6 +851,50 @@ def mbconv_fused(exp, exp_act: int, dw, dw_act: int, proj, proj_act: int, x: NHW
           _ptr(dw.packed), _ptr(dw.scale), _ptr(dw.shift), _ptr(proj.packed), _ptr(proj.scale),
           _ptr(proj.shift), _ptr(residual.t) if residual is not None else None, _ptr(y))
     return NHWC(y, x.N, Ho, Wo, proj.conv.out_channels, cpitch=Cout)
+
+
+def bottleneck_fused(c1, act1: int, c2, act2: int, c3, act3: int, x: NHWC, post_act: int, idr=None, probe=False):
+    """A whole bottleneck unit - 1x1 -> 3x3 -> 1x1, + skip, + post_act - as ONE launch (pcv_bottleneck_fused): `c1`, `c2`, `c3` are
+    the ConvRunners of the body's blocks; the skip is `x` itself or, with `idr` (the runner of the unit's `identity_conv`), that
+    convolution of `x`, computed inside the launch. Returns the unit output, or None when the unit is not covered (the caller then
+    issues the separate launches). `probe`: `x` is a _ShapeOnly; returns whether a dense input of that shape would be covered."""
+    runners = (c1, c2, c3) + ((idr,) if idr is not None else ())
+    if not FUSE_UNITS or not (probe or x.dense) or any(r.depthwise or r.pad4 is not None for r in runners):
+        return None
+    _require_eval(*runners)
+    # every bottleneck unit of every stage asks on every forward, and an eager forward at batch 1 is bound by this host code: what the
+    # library refused once for a shape is not asked again (three descriptors and a call per unit; a refusal only ever means the
+    # separate launches, so a remembered one is safe even if pcv_set_tuning("bnu", ...) changes later)
+    key = (x.N, x.H, x.W, x.dtype, x.cpitch, act1, act2, act3, post_act, idr is not None)
+    refused = c1.__dict__.setdefault("_bnu_refused", set())
+    if key in refused:
+        return None
+    d1 = c1.desc(x, act1, 0, False)
+    t1 = _ShapeOnly(x.N, x.H, x.W, c1.conv.out_channels, x.dtype)
+    d2 = c2.desc(t1, act2, 0, False)
+    if _conv_out(d2, x.H, x.W) != (x.H, x.W):
+        refused.add(key)
+        return None
+    t2 = _ShapeOnly(x.N, x.H, x.W, c2.conv.out_channels, x.dtype)
+    d3 = c3.desc(t2, act3, post_act, True)
+    di = idr.desc(x, 0, 0, False) if idr is not None else None
+    if not _lib.lib().pcv_bottleneck_supported(ctypes.byref(d1), ctypes.byref(d2), ctypes.byref(d3),
+                                               ctypes.byref(di) if di is not None else None):
+        refused.add(key)
+        return None
+    if probe:
+        return True
+    c1.prepare(x, d1)
+    c2.prepare(_PrepHandle(t1, x.device), d2)
+    c3.prepare(_PrepHandle(t2, x.device), d3)
+    if idr is not None:
+        idr.prepare(x, di)
+    y = torch.empty((x.N, x.H, x.W, d3.Cout), dtype=x.dtype, device=x.device)
+    _call(x.device, "bottleneck_fused", ctypes.byref(d1), ctypes.byref(d2), ctypes.byref(d3), ctypes.byref(di) if di is not None else None,
+          _ptr(x.t), _ptr(c1.packed), _ptr(c1.scale), _ptr(c1.shift), _ptr(c2.packed), _ptr(c2.scale), _ptr(c2.shift),
+          _ptr(c3.packed), _ptr(c3.scale), _ptr(c3.shift), _ptr(idr.packed) if idr is not None else None,
+          _ptr(idr.scale) if idr is not None else None, _ptr(idr.shift) if idr is not None else None, _ptr(y))
+    return NHWC(y, x.N, x.H, x.W, c3.conv.out_channels, cpitch=d3.Cout)
 
 
 class _PrepHandle(object):

@@ -7,7 +7,7 @@
 
 __all__ = ['conv1x1', 'conv3x3', 'depthwise_conv3x3', 'ConvBlock', 'conv1x1_block', 'conv3x3_block', 'conv5x5_block',
            'conv7x7_block', 'dwconv_block', 'dwconv3x3_block', 'dwconv5x5_block', 'DwsConvBlock', 'dwsconv3x3_block', 'BareConv', 'PreConvBlock',
-           'pre_conv1x1_block', 'pre_conv3x3_block', 'conv_block_pair', 'conv_block_maxpool', 'mbconv_chain']
+           'pre_conv1x1_block', 'pre_conv3x3_block', 'conv_block_pair', 'conv_block_maxpool', 'mbconv_chain', 'conv_block_bottleneck']
 
 import torch.nn as nn
 from .activ import lambda_relu, create_activation_layer
@@ -131,6 +131,26 @@ def mbconv_chain(exp_block, dw_block, proj_block, x, residual=None, post_act=Non
     return engine.mbconv_fused(exp_block._pcv_runner if exp_block is not None else None,
                                code(exp_block) if exp_block is not None else 0, dw_block._pcv_runner, code(dw_block),
                                proj_block._pcv_runner, code(proj_block), x, residual, engine.act_code(post_act))
+
+
+def conv_block_bottleneck(conv1, conv2, conv3, x, post_act, id_block=None, probe=False):
+    """The ConvBlocks of a bottleneck body - 1x1 -> 3x3 -> 1x1 - with the unit's skip add (`x`, or `id_block(x)` for a unit with an
+    identity convolution) and the activation behind it as one fused launch when the unit is covered (pcv_bottleneck_fused), else
+    None: the caller then runs the blocks one by one. `probe`: `x` is only a shape (engine.ShapeOnly), nothing is launched, the answer
+    is whether such a unit would be covered."""
+    blocks = (conv1, conv2, conv3) + ((id_block,) if id_block is not None else ())
+    if not isinstance(x, engine.ShapeOnly if probe else engine.NHWC) or not all(isinstance(b, ConvBlock) for b in blocks):
+        return None
+    if id_block is not None and id_block.activate:
+        return None
+    for blk in blocks:
+        if blk._pcv_runner is None:
+            blk._pcv_runner = engine.ConvRunner(blk.conv, blk.bn if blk.normalize else None, pad4=blk._pad4)
+
+    def code(blk):
+        return engine.act_code(blk.activ) if blk.activate else 0
+    return engine.bottleneck_fused(conv1._pcv_runner, code(conv1), conv2._pcv_runner, code(conv2), conv3._pcv_runner, code(conv3), x,
+                                   engine.act_code(post_act), id_block._pcv_runner if id_block is not None else None, probe=probe)
 
 
 def conv1x1_block(padding=0, **kwargs):

@@ -11,7 +11,7 @@ __all__ = ['ResNet', 'resnet10', 'resnet12', 'resnet14', 'resnetbc14b', 'resnet1
 import torch.nn as nn
 from .common.activ import lambda_relu
 from .common.norm import lambda_batchnorm2d
-from .common.conv import conv1x1_block, conv3x3_block, conv7x7_block, conv_block_pair, conv_block_maxpool
+from .common.conv import conv1x1_block, conv3x3_block, conv7x7_block, conv_block_pair, conv_block_maxpool, conv_block_bottleneck
 from ._tail import MaxPool2dNHWC, AvgPool2dNHWC, LinearHead, run_net, maybe_load_pretrained, init_conv_params, DEFAULT_ROOT
 from .. import engine
 
@@ -76,8 +76,14 @@ class ResUnit(nn.Module):
         """Stage-level execution of a bottleneck unit: `conv1_out` is this unit's first convolution when the previous unit
         already produced it; with `next_unit`, the last convolution (+ skip add + ReLU) and the next unit's first
         convolution go out as one launch whenever the pair is covered. Returns (unit output, next unit's conv1 output
-        or None)."""
+        or None). A unit the fused bottleneck kernel covers (stage 1) runs as that one launch instead and hands nothing on."""
         body = self.body
+        fused = conv_block_bottleneck(body.conv1, body.conv2, body.conv3, a, self.activ,
+                                      id_block=self.identity_conv if self.resize_identity else None)
+        if fused is not None:
+            return fused, None
+        if next_unit is not None and isinstance(next_unit, ResUnit) and self._stride1() and next_unit.fuses_whole(a):
+            next_unit = None        # the next unit computes its own first convolution inside its launch: do not ask the pair for it
         y = body.conv2(conv1_out if conv1_out is not None else body.conv1(a))
         if next_unit is not None and self.resize_identity:
             # the skip convolution recomputed inside the fused pair (no launch, no 4x wider tensor written and re-read)
@@ -90,6 +96,18 @@ class ResUnit(nn.Module):
             if pair is not None:
                 return pair
         return body.conv3(y, residual=identity, post_act=self.activ), None
+
+    def _stride1(self):
+        return all(tuple(b.conv.stride) == (1, 1) for b in (self.body.conv1, self.body.conv2, self.body.conv3))
+
+    def fuses_whole(self, a_prev):
+        """Whether this unit will run as the fused bottleneck launch when it follows, at stride 1, a unit whose input is `a_prev`."""
+        if not isinstance(self.body, ResBottleneck) or not isinstance(a_prev, engine.NHWC):
+            return False
+        body = self.body
+        x = engine.ShapeOnly(a_prev.N, a_prev.H, a_prev.W, body.conv1.conv.in_channels, a_prev.dtype)
+        return conv_block_bottleneck(body.conv1, body.conv2, body.conv3, x, self.activ,
+                                     id_block=self.identity_conv if self.resize_identity else None, probe=True)
 
     def forward(self, x):
         return engine.boundary(self, x, self._run)

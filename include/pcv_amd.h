@@ -36,7 +36,8 @@ extern "C" {
  *    (still 5: + pcv_resize_plan_bytes / pcv_resize_plan / pcv_resize_crop_u8 - pure additions, no signature, struct or blob of
  *    version 5 changes, so a version-5 binding keeps working against this library and the number does not move;
  *    likewise + pcv_classify_f32, + pcv_cbam_pool / _excite / _spatial_pool / _apply,
- *    + pcv_mixconv_packed_bytes / pcv_mixconv_pack / pcv_mixconv2d_fused, + pcv_bottleneck_supported / pcv_bottleneck_fused) */
+ *    + pcv_mixconv_packed_bytes / pcv_mixconv_pack / pcv_mixconv2d_fused, + pcv_bottleneck_supported / pcv_bottleneck_fused,
+ *    + pcv_instnorm_workspace_bytes / pcv_instnorm_act) */
 #define PCV_ABI_VERSION 5
 
 typedef struct pcv_ctx pcv_ctx;
@@ -403,6 +404,25 @@ int pcv_mbconv_fused(pcv_ctx* ctx, const pcv_conv_desc* d_exp, const pcv_conv_de
  * y is dense. */
 int pcv_bn_act(pcv_ctx* ctx, const void* x, const float* scale, const float* shift, void* y, long rows, int C,
                int x_cpitch, int act, int dtype, void* stream);
+
+/* nn.InstanceNorm2d(affine=True) at inference on the leading Cn of C channels of NHWC x[N, HW, x_cpitch], then the activation:
+ *     c <  Cn : y[n,p,c] = act(gamma[c] * (x[n,p,c] - mean[n,c]) * rsqrt(var[n,c] + eps) + beta[c])
+ *     c >= Cn : y[n,p,c] = act(x[n,p,c])
+ * mean / var (biased) are taken over the HW positions of image n and channel c: the statistics of the image in flight, no
+ * running ones, so nothing folds at load time. This is IBN (common/norm.py:118-162, inst_first=True: InstanceNorm2d on the first
+ * floor(C / 2) channels, BatchNorm2d - folded into the producing convolution, whose scale / shift are (1, 0) on the IN half - on the
+ * rest) behind conv1 of an IBNResBottleneck (ibnresnet.py; ibnresnext.py), and with Cn == C the whole-tensor norms of the
+ * b-variant (ibnbresnet.py: after the stem convolution, and after the skip add of the last unit of stages 1 and 2). Cn == 0 is a
+ * plain activation pass. Two launches on `stream`, nothing else (capturable): the statistics kernel leaves
+ * (gamma * rstd, beta - mean * gamma * rstd) as fp32 [N, Cn, 2] in `workspace` (pcv_instnorm_workspace_bytes; 16-byte aligned, may
+ * be NULL together with gamma / beta when Cn == 0), one pass with shifted sums merged by Chan's formula in a fixed tree - an
+ * image's result does not depend on its place in the batch - and the second is pcv_bn_act's pass with per-(image, channel)
+ * coefficients. gamma, beta: fp32 [Cn]. y is dense [N, HW, C] in `dtype`; fp16 results go through the range guard.
+ * Refused with PCV_ERR_INVALID before any device call: NULL pointers; N, HW, C <= 0; Cn < 0 or > C; C, Cn or x_cpitch (0 = C) not
+ * a multiple of 8; x_cpitch < C; eps <= 0 or not finite; unknown act or dtype. PCV_ERR_TOO_LARGE: x beyond the 2 GiB window. */
+int pcv_instnorm_workspace_bytes(int N, int Cn, size_t* bytes);
+int pcv_instnorm_act(pcv_ctx* ctx, const void* x, const float* gamma, const float* beta, void* y, void* workspace, int N, int HW,
+                     int C, int Cn, int x_cpitch, float eps, int act, int dtype, void* stream);
 
 /* ---- multi-GPU: RCCL helpers for a C caller -------------------------------------------------------------------------------------
  * The reference has no distributed code; BASELINE's north star shards the batch over the 8 GPUs of a node - one

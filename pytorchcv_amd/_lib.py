@@ -103,6 +103,8 @@ _SIGS = {
     "pcv_mbconv_fused": (_I, [_VP, ctypes.POINTER(ConvDesc), ctypes.POINTER(ConvDesc), ctypes.POINTER(ConvDesc), _VP, _VP, _VP, _VP,
                               _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "pcv_bn_act": (_I, [_VP, _VP, _VP, _VP, _VP, ctypes.c_long, _I, _I, _I, _I, _VP]),
+    "pcv_instnorm_workspace_bytes": (_I, [_I, _I, ctypes.POINTER(ctypes.c_size_t)]),
+    "pcv_instnorm_act": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, ctypes.c_float, _I, _I, _VP]),
     "pcv_se_scale": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _VP]),
     "pcv_splat_squeeze": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _VP]),
     "pcv_splat_excite": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _VP]),

@@ -42,6 +42,7 @@ MIX_INSTANCES(MIX_DECLARE, PCV_BF16)
 MIX_INSTANCES(MIX_DECLARE, PCV_F16)
 #include "aux_kernels.hpp"
 #include "cbam_kernels.hpp"
+#include "instnorm.hpp"
 #include "resize_kernel.hpp"
 #include "classify_kernel.hpp"
 #include "head_gemm.hpp"
@@ -2611,6 +2612,44 @@ int pcv_bn_act(pcv_ctx* ctx, const void* x, const float* scale, const float* shi
     if (int rc = stream_grid(ctx, "pcv_bn_act", total8, &blocks)) return rc;
     hipStream_t st = (hipStream_t)stream;
     for_dtype(dtype, [&](auto T) { bn_act_kernel<DT_OF(T)><<<blocks, 256, 0, st>>>(x, scale, shift, y, total8, C, x_cpitch, act, ctx->ovf); });
+    return launched(ctx);
+}
+
+int pcv_instnorm_workspace_bytes(int N, int Cn, size_t* bytes) {
+    if (!bytes || N <= 0 || Cn < 0 || Cn % 8 != 0)
+        return fail(nullptr, PCV_ERR_INVALID, "pcv_instnorm_workspace_bytes: bad argument (N > 0, Cn >= 0 and a multiple of 8)");
+    *bytes = (size_t)N * (size_t)Cn * 2 * sizeof(float);
+    return PCV_OK;
+}
+
+int pcv_instnorm_act(pcv_ctx* ctx, const void* x, const float* gamma, const float* beta, void* y, void* workspace, int N, int HW,
+                     int C, int Cn, int x_cpitch, float eps, int act, int dtype, void* stream) {
+    PCV_ENTER(ctx);
+    if (x_cpitch <= 0) x_cpitch = C;
+    if (!x || !y || N <= 0 || HW <= 0 || C <= 0 || Cn < 0 || Cn > C || C % 8 != 0 || Cn % 8 != 0 || x_cpitch < C || x_cpitch % 8 != 0 ||
+        !(eps > 0.f) || !std::isfinite(eps) || !dtype_ok(dtype) || act < 0 || act > PCV_ACT_HSWISH)
+        return fail(ctx, PCV_ERR_INVALID,
+                    "pcv_instnorm_act: bad argument (N, HW, C > 0; 0 <= Cn <= C; C, Cn and x_cpitch multiples of 8; x_cpitch >= C; eps > 0)");
+    if (Cn > 0 && (!gamma || !beta || !workspace || !aligned16(workspace)))
+        return fail(ctx, PCV_ERR_INVALID, "pcv_instnorm_act: gamma, beta and a 16-byte aligned workspace are needed when Cn > 0");
+    if (!in_window((unsigned long long)N * HW * x_cpitch * esize(dtype))) return too_large(ctx, "pcv_instnorm_act", "x");
+    const long long bpi = ((long long)HW * (C / 8) + 255) / 256;          // apply: blocks per image, 256 chunks each
+    unsigned blocks = 0;
+    if (int rc = stream_grid(ctx, "pcv_instnorm_act", (long long)N * bpi * 256, &blocks)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    float* ws = reinterpret_cast<float*>(workspace);
+    if (Cn > 0) {
+        const int groups = (Cn / 8 + kInGroup - 1) / kInGroup;
+        const long long items = (long long)N * groups;          // < 2^31: N * Cn * 2 <= the bytes of x
+        const unsigned sgrid = (unsigned)cap_blocks(ctx, items);
+        for_dtype(dtype, [&](auto T) {
+            instnorm_stats_kernel<DT_OF(T)><<<sgrid, kInThreads, 0, st>>>(x, gamma, beta, ws, HW, Cn, x_cpitch, eps, groups, (int)items);
+        });
+        if (int rc = launched(ctx)) return rc;
+    }
+    for_dtype(dtype, [&](auto T) {
+        instnorm_apply_kernel<DT_OF(T)><<<blocks, 256, 0, st>>>(x, ws, y, (unsigned)(N * bpi), (unsigned)bpi, HW, C, Cn, x_cpitch, act, ctx->ovf);
+    });
     return launched(ctx);
 }
 

@@ -5,7 +5,7 @@
 """
 
 __all__ = ['NHWC', 'DTYPES', 'default_dtype', 'set_compute_dtype', 'compute_dtype_of', 'Fp16Guard', 'fp16_overflow_count', 'from_nchw', 'to_nchw', 'ConvRunner',
-           'MixConvRunner', 'BnActRunner', 'maxpool2d', 'avgpool2d', 'avgpool2d_pad', 'global_avgpool', 'se_excite', 'se_scale', 'se_forward', 'splat_forward', 'cbam_channel_gate', 'cbam_spatial', 'cbam_forward', 'channel_slice', 'cat_shuffle2', 'act_code',
+           'MixConvRunner', 'BnActRunner', 'IBNConvRunner', 'InstNormRunner', 'maxpool2d', 'avgpool2d', 'avgpool2d_pad', 'global_avgpool', 'se_excite', 'se_scale', 'se_forward', 'splat_forward', 'cbam_channel_gate', 'cbam_spatial', 'cbam_forward', 'channel_slice', 'cat_shuffle2', 'act_code',
            'boundary', 'round8', 'channel_concat_into', 'interpolate', 'add', 'classify']
 
 import os
@@ -964,6 +964,76 @@ class BnActRunner(object):
         y = torch.empty((x.N, x.H, x.W, CP), dtype=x.dtype, device=x.device)
         _call(x.device, "bn_act", _ptr(x.t), _ptr(self.scale), _ptr(self.shift), _ptr(y), x.N * x.H * x.W, CP, x.cpitch, act,
               _CODE_OF_TORCH[x.dtype])
+        return NHWC(y, x.N, x.H, x.W, x.C, cpitch=CP)
+
+
+class IBNConvRunner(ConvRunner):
+    """A convolution whose output goes through IBN (common/norm.py `IBN`): the BatchNorm2d of the second channel section folds into
+    the epilogue as usual, the InstanceNorm2d section leaves the convolution untouched - scale 1, shift 0 (+ the convolution's
+    bias) - for `InstNormRunner` to normalise with the statistics of the image in flight."""
+    def __init__(self, conv: nn.Conv2d, ibn, pad4=None):
+        super(IBNConvRunner, self).__init__(conv, None, pad4=pad4)
+        self.ibn = ibn
+
+    def _sources(self):
+        bn = self.ibn.batch_norm
+        return [self.conv.weight, self.conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var]
+
+    def prepare(self, x: NHWC, d: ConvDesc):
+        before = self._key
+        super(IBNConvRunner, self).prepare(x, d)
+        if self._key == before:
+            return
+        bn, dev = self.ibn.batch_norm, x.device
+        h1, h2 = self.ibn.split_sections
+        if d.Cout != h1 + h2 or bn.num_features != h2:
+            raise RuntimeError("IBN sections {} do not cover the convolution's {} output channels".format((h1, h2), d.Cout))
+        g, b, m, v = [t.detach().float().contiguous() for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)]
+        bias = self.conv.bias[h1:].detach().float().contiguous() if self.conv.bias is not None else None
+        scale = torch.empty(h2, dtype=torch.float32, device=dev)
+        shift = torch.empty(h2, dtype=torch.float32, device=dev)
+        _call(dev, "bn_fold", h2, _ptr(g), _ptr(b), _ptr(m), _ptr(v), ctypes.c_float(bn.eps), _ptr(bias), _ptr(scale), _ptr(shift))
+        self.scale[h1:].copy_(scale)
+        self.shift[h1:].copy_(shift)
+        torch.cuda.current_stream(dev).synchronize()
+
+    def run(self, x: NHWC, *args, **kwargs) -> NHWC:
+        if self.ibn.batch_norm.training:
+            raise RuntimeError("pytorchcv_amd is an inference path: call net.eval() first (BatchNorm is folded)")
+        return super(IBNConvRunner, self).run(x, *args, **kwargs)
+
+
+class InstNormRunner(object):
+    """nn.InstanceNorm2d(affine=True) at inference + activation on the leading `norm.num_features` channels of a handle, the rest
+    only activated (pcv_instnorm_act: two launches, statistics then apply). Nothing folds at load time - the statistics are those
+    of the image in flight - so the runner keeps no derived state: gamma / beta are read where the module holds them (fp32)."""
+    def __init__(self, norm):
+        if not isinstance(norm, nn.InstanceNorm2d):
+            raise NotImplementedError("InstNormRunner runs nn.InstanceNorm2d, got {}".format(type(norm).__name__))
+        if not norm.affine or norm.track_running_stats:
+            raise NotImplementedError("only InstanceNorm2d(affine=True, track_running_stats=False) is on the MI355X path")
+        if norm.num_features % 8:
+            raise NotImplementedError("InstanceNorm2d over {} channels: the MI355X path needs a multiple of 8".format(norm.num_features))
+        self.norm = norm
+
+    def run(self, x: NHWC, act: int) -> NHWC:
+        norm = self.norm
+        if x.wpitch != x.W:
+            raise RuntimeError("InstanceNorm on a row-padded handle")
+        Cn, CP = norm.num_features, round8(x.C)
+        if Cn > x.C or x.C % 8:
+            raise RuntimeError("InstanceNorm2d over the first {} channels of a handle with {}".format(Cn, x.C))
+        if norm.weight.device != x.device:
+            raise RuntimeError("model parameters are on {} but the input is on {}".format(norm.weight.device, x.device))
+        gamma = norm.weight.detach().float().contiguous()        # (no copy for fp32 parameters)
+        beta = norm.bias.detach().float().contiguous()
+        nbytes = ctypes.c_size_t(0)
+        if _lib.lib().pcv_instnorm_workspace_bytes(x.N, Cn, ctypes.byref(nbytes)) != 0:
+            raise _lib.PcvError(-1, "pcv_instnorm_workspace_bytes({}, {})".format(x.N, Cn))
+        ws = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=x.device)
+        y = torch.empty((x.N, x.H, x.W, CP), dtype=x.dtype, device=x.device)
+        _call(x.device, "instnorm_act", _ptr(x.t), _ptr(gamma), _ptr(beta), _ptr(y), _ptr(ws), x.N, x.H * x.W, CP, Cn, x.cpitch,
+              ctypes.c_float(norm.eps), act, _CODE_OF_TORCH[x.dtype])
         return NHWC(y, x.N, x.H, x.W, x.C, cpitch=CP)
 
 

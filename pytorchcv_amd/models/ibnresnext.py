@@ -1,0 +1,95 @@
+"""
+    IBN-ResNeXt for ImageNet-1K on the MI355X hot path (https://arxiv.org/abs/1807.09441; reference
+    pytorchcv/models/ibnresnext.py): IBN-ResNet's unit with the grouped 3x3 of ResNeXt. conv1 of stages 1-3 goes through IBN
+    (one convolution launch + pcv_instnorm_act), stage 4 is ResNeXt's own unit with its fused routes.
+"""
+
+__all__ = ['IBNResNeXt', 'ibn_resnext50_32x4d', 'ibn_resnext101_32x4d', 'ibn_resnext101_64x4d', 'IBNResNeXtBottleneck',
+           'IBNResNeXtUnit', 'get_ibnresnext']
+
+import math
+import torch.nn as nn
+from .common.conv import conv1x1_block, conv3x3_block
+from .resnet import ResInitBlock, ResStage
+from .resnext import ResNeXtUnit
+from .ibnresnet import ibn_conv1x1_block
+from ._build import ClassifierNet, add_stages, stage_table
+from ._tail import maybe_load_pretrained, DEFAULT_ROOT
+from .. import engine
+
+
+class IBNResNeXtBottleneck(nn.Module):
+    """1x1 (IBN) -> grouped 3x3 (carries the stride) -> 1x1 (reference ibnresnext.py:16-65)."""
+    def __init__(self, in_channels, out_channels, stride, cardinality, bottleneck_width, conv1_ibn):
+        super(IBNResNeXtBottleneck, self).__init__()
+        mid_channels = out_channels // 4
+        D = int(math.floor(mid_channels * (bottleneck_width / 64.0)))
+        group_width = cardinality * D
+        self.conv1 = ibn_conv1x1_block(in_channels=in_channels, out_channels=group_width, use_ibn=conv1_ibn)
+        self.conv2 = conv3x3_block(in_channels=group_width, out_channels=group_width, stride=stride, groups=cardinality)
+        self.conv3 = conv1x1_block(in_channels=group_width, out_channels=out_channels, activation=None)
+
+    def forward(self, x, residual=None, post_act=None):
+        return engine.boundary(self, x, lambda a: self.conv3(self.conv2(self.conv1(a)), residual=residual, post_act=post_act))
+
+
+class IBNResNeXtUnit(nn.Module):
+    """relu(body(x) + identity) (reference ibnresnext.py:68-120); not chainable, as IBNResUnit."""
+    def __init__(self, in_channels, out_channels, stride, cardinality, bottleneck_width, conv1_ibn):
+        super(IBNResNeXtUnit, self).__init__()
+        self.resize_identity = (in_channels != out_channels) or (stride != 1)
+        self.body = IBNResNeXtBottleneck(in_channels=in_channels, out_channels=out_channels, stride=stride,
+                                         cardinality=cardinality, bottleneck_width=bottleneck_width, conv1_ibn=conv1_ibn)
+        if self.resize_identity:
+            self.identity_conv = conv1x1_block(in_channels=in_channels, out_channels=out_channels, stride=stride, activation=None)
+        self.activ = nn.ReLU(inplace=True)
+
+    def _run(self, a):
+        identity = self.identity_conv(a) if self.resize_identity else a
+        return self.body(a, residual=identity, post_act=self.activ)
+
+    def forward(self, x):
+        return engine.boundary(self, x, self._run)
+
+
+class IBNResNeXt(ClassifierNet):
+    """`features` (init_block, stage1..4, final_pool) + `output` Linear (reference ibnresnext.py:123-197)."""
+    pcv_16bit = "fp16"      # the 16-bit mode "auto" resolves to for this family (engine.compute_dtype_of)
+
+    def __init__(self, channels, init_block_channels, cardinality, bottleneck_width, in_channels=3, in_size=(224, 224),
+                 num_classes=1000):
+        super(IBNResNeXt, self).__init__(in_size, num_classes)
+        self.features.add_module("init_block", ResInitBlock(in_channels=in_channels, out_channels=init_block_channels))
+
+        def make_unit(cin, cout, stride, i, j):
+            if cout < 2048:                 # (reference ibnresnext.py:166)
+                return IBNResNeXtUnit(in_channels=cin, out_channels=cout, stride=stride, cardinality=cardinality,
+                                      bottleneck_width=bottleneck_width, conv1_ibn=True)
+            return ResNeXtUnit(in_channels=cin, out_channels=cout, stride=stride, cardinality=cardinality,
+                               bottleneck_width=bottleneck_width)
+        width = add_stages(self.features, init_block_channels, channels, container=ResStage, make_unit=make_unit)
+        self.finish(width)
+        engine.stamp_family_dtype(self)                    # sub-modules called on their own resolve "auto" like the net
+
+
+_DEPTHS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3)}
+
+
+def get_ibnresnext(blocks, cardinality, bottleneck_width, model_name=None, pretrained=False, root=DEFAULT_ROOT, **kwargs):
+    if blocks not in _DEPTHS:
+        raise ValueError("Unsupported IBN-ResNeXt with number of blocks: {}".format(blocks))
+    net = IBNResNeXt(channels=stage_table((256, 512, 1024, 2048), _DEPTHS[blocks]), init_block_channels=64,
+                     cardinality=cardinality, bottleneck_width=bottleneck_width, **kwargs)
+    return maybe_load_pretrained(net, model_name, pretrained, root)
+
+
+def ibn_resnext50_32x4d(**kwargs):
+    return get_ibnresnext(blocks=50, cardinality=32, bottleneck_width=4, model_name="ibn_resnext50_32x4d", **kwargs)
+
+
+def ibn_resnext101_32x4d(**kwargs):
+    return get_ibnresnext(blocks=101, cardinality=32, bottleneck_width=4, model_name="ibn_resnext101_32x4d", **kwargs)
+
+
+def ibn_resnext101_64x4d(**kwargs):
+    return get_ibnresnext(blocks=101, cardinality=64, bottleneck_width=4, model_name="ibn_resnext101_64x4d", **kwargs)

@@ -135,6 +135,8 @@ def synth_state_dict(template: dict, seed: int = 1234, calib: dict | None = None
         elif leaf == "weight" and len(shape) == 2:
             bound = float(1.0 / np.sqrt(np.float64(shape[1])))
             v = _uniform_pm_f32(seed, st, n, bound)
+        elif leaf == "weight" and len(shape) == 1:
+            v = 0.5 + hash_uniform(seed, st, n)                 # InstanceNorm2d(affine) gamma: no running statistics beside it
         elif leaf == "bias":
             v = (hash_uniform(seed, st, n) * 2.0 - 1.0) * 0.1
         else:

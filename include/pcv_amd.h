@@ -37,7 +37,8 @@ extern "C" {
  *    version 5 changes, so a version-5 binding keeps working against this library and the number does not move;
  *    likewise + pcv_classify_f32, + pcv_cbam_pool / _excite / _spatial_pool / _apply,
  *    + pcv_mixconv_packed_bytes / pcv_mixconv_pack / pcv_mixconv2d_fused, + pcv_bottleneck_supported / pcv_bottleneck_fused,
- *    + pcv_instnorm_workspace_bytes / pcv_instnorm_act) */
+ *    + pcv_instnorm_workspace_bytes / pcv_instnorm_act, + pcv_ghost_supported / pcv_ghost_dw_fused and the activation code
+ *    PCV_ACT_CLAMP01) */
 #define PCV_ABI_VERSION 5
 
 typedef struct pcv_ctx pcv_ctx;
@@ -52,10 +53,12 @@ typedef enum pcv_status {
 
 typedef enum pcv_dtype { PCV_F32 = 0, PCV_BF16 = 1, PCV_F16 = 2 } pcv_dtype;
 
-/* activ.py:50-81,117-132 (relu, relu6, sigmoid) and activ.py:16-47 (swish, hsigmoid, hswish) */
+/* activ.py:50-81,117-132 (relu, relu6, sigmoid) and activ.py:16-47 (swish, hsigmoid, hswish); CLAMP01 = clamp(x, 0, 1), GhostNet's
+ * GhostHSigmoid (ghostnet.py:18-24): honoured by pcv_se_excite, pcv_fc_f32 and pcv_ghost_dw_fused; the other descriptor-based entry
+ * points take the codes up to PCV_ACT_HSWISH */
 typedef enum pcv_act {
     PCV_ACT_NONE = 0, PCV_ACT_RELU = 1, PCV_ACT_RELU6 = 2, PCV_ACT_SIGMOID = 3,
-    PCV_ACT_SWISH = 4, PCV_ACT_HSIGMOID = 5, PCV_ACT_HSWISH = 6
+    PCV_ACT_SWISH = 4, PCV_ACT_HSIGMOID = 5, PCV_ACT_HSWISH = 6, PCV_ACT_CLAMP01 = 7
 } pcv_act;
 
 /*
@@ -250,6 +253,27 @@ int pcv_mixconv_pack(pcv_ctx* ctx, const pcv_conv_desc* d, const int* kernels, i
                      void* stream);
 int pcv_mixconv2d_fused(pcv_ctx* ctx, const pcv_conv_desc* d, const int* kernels, int nk, const void* x, const void* packed,
                         const float* scale, const float* shift, void* y, void* stream);
+/* The second half of GhostNet's ghost module as ONE launch: `y = self.cheap_conv(x); return torch.cat((x, y), dim=1)` of
+ * GhostConvBlock.forward (ghostnet.py:57-60; cheap_conv = depthwise 3x3 Conv2d + BatchNorm2d(eval) + activation) and, with a residual,
+ * the `x = x + identity` of GhostUnit.forward behind the unit's last ghost module (ghostnet.py:167-174):
+ *   y[.., c]      = m[.., c]                                     + residual[.., c]          c in [0, Cm)
+ *   y[.., Cm + c] = act(scale[c] * dw3x3(m)[.., c] + shift[c])   + residual[.., Cm + c]
+ * m is the main convolution's output, NHWC [N,H,W,round8(Cm)] (pad channels are never read); y and residual are dense NHWC
+ * [N,H,W,2 Cm]. No depthwise output tensor, no concatenation copy, no separate add; the channel offset Cm need not be a multiple of 8.
+ * `d` is a depthwise descriptor with Cin == Cout == groups == Cm (LOGICAL, Cm % 4 == 0), 3x3, stride 1, pads 1, x_cpitch = round8(Cm)
+ * (the pitch of m, of the taps and of scale / shift), y_cpitch 0 or 2 Cm, act = any pcv_act code (cheap half only: the main half carries
+ * the activation of the convolution that produced it), post_act 0. `packed` is what pcv_dwconv_pack produces for a 3x3 depthwise layer
+ * of round8(Cm) channels (only its first part, [9][round8(Cm)], is read). fp32 accumulation; fp16 results - the cheap half and both
+ * sums with the residual - are range-guarded. Without a residual the main half is a bit copy of m.
+ * Refused with PCV_ERR_INVALID and a text before any device call: a stale descriptor size, groups != Cin or Cin != Cout, Cm % 4 != 0,
+ * a window other than 3x3, stride other than 1, pads other than 1, dilation, post_act, x_cpitch other than round8(Cm), a padded row
+ * pitch, y_cpitch other than 0 / 2 Cm, out_dtype != dtype, has_residual with a NULL residual, an empty input, pointers that are not
+ * 16-byte aligned; PCV_ERR_TOO_LARGE when m exceeds the 2 GiB window of one launch.
+ *   pcv_ghost_supported   host arithmetic only: 1 when pcv_ghost_dw_fused takes `d`, else 0 with the reason in pcv_last_error(NULL)
+ *   pcv_ghost_dw_fused    the launch: no allocation, no synchronisation (capturable). */
+int pcv_ghost_supported(const pcv_conv_desc* d);
+int pcv_ghost_dw_fused(pcv_ctx* ctx, const pcv_conv_desc* d, const void* m, const void* packed, const float* scale,
+                       const float* shift, const void* residual, void* y, void* stream);
 /* nn.MaxPool2d(k, s, p, ceil_mode) of ResInitBlock (resnet.py:255-258, floor) and ShuffleInitBlock (shufflenetv2.py:111-115,
  * ceil_mode=True): -inf padding; with ceil_mode the last window may hang over the bottom / right edge (PyTorch's rule). A NaN
  * in a window gives NaN, as in torch. y is [N, Ho, Wo, C] with PyTorch's output size; an empty one is PCV_ERR_INVALID. */

@@ -40,6 +40,10 @@ MBR_SHAPES(MBR_DECLARE, PCV_F16)
 MIX_INSTANCES(MIX_DECLARE, PCV_F32)
 MIX_INSTANCES(MIX_DECLARE, PCV_BF16)
 MIX_INSTANCES(MIX_DECLARE, PCV_F16)
+#include "ghost.hpp"
+GHOST_INSTANCES(GHOST_DECLARE, PCV_F32)
+GHOST_INSTANCES(GHOST_DECLARE, PCV_BF16)
+GHOST_INSTANCES(GHOST_DECLARE, PCV_F16)
 #include "aux_kernels.hpp"
 #include "cbam_kernels.hpp"
 #include "instnorm.hpp"
@@ -743,6 +747,10 @@ static MbLds mbconv_plan(int stride, bool expand, int ka, int nChunks, int nRowT
 #define MIX_ROW(DT, S, FAST) {MIX_KERNEL(DT, S, FAST, 2), MIX_KERNEL(DT, S, FAST, 3), MIX_KERNEL(DT, S, FAST, 4), MIX_KERNEL(DT, S, FAST, 5)}
 #define MIX_TYPE(DT) {{MIX_ROW(DT, 1, false), MIX_ROW(DT, 1, true)}, {MIX_ROW(DT, 2, false), MIX_ROW(DT, 2, true)}}
 static const Kernel kMix[3][2][2][4] = {MIX_TYPE(PCV_F32), MIX_TYPE(PCV_BF16), MIX_TYPE(PCV_F16)};
+
+// ghost module (ghost.hpp): [storage type][clamp-only activation]; no dynamic LDS
+#define GHOST_ROW(DT) {kernel_of(ghost_dw_kernel<DT, false>, 256, 0), kernel_of(ghost_dw_kernel<DT, true>, 256, 0)}
+static const Kernel kGhost[3][2] = {GHOST_ROW(PCV_F32), GHOST_ROW(PCV_BF16), GHOST_ROW(PCV_F16)};
 
 // top-k / softmax / label rank (classify_kernel.hpp): one wave per row up to 1024 entries, four above; LDS = scratch + the row
 static Kernel classify_kernel_of(int J) {
@@ -1916,6 +1924,81 @@ int pcv_mixconv2d_fused(pcv_ctx* ctx, const pcv_conv_desc* d, const int* kernels
     }
     const Kernel& K = kMix[d->dtype == PCV_F32 ? 0 : (d->dtype == PCV_BF16 ? 1 : 2)][d->stride_h - 1][d->act <= PCV_ACT_RELU6 ? 1 : 0][nk - 2];
     return launch(ctx, K, (unsigned)blocks, (hipStream_t)stream, p);
+}
+
+// ---- ghost module: cheap depthwise 3x3 + concatenation + skip add (ghost.hpp) ------------------------------------------------------
+// every check of the descriptor alone (the pointer checks are the launch's)
+static const char* check_ghost(const pcv_conv_desc& d) {
+    if (desc_stale(d)) return kStaleDesc;
+    if (!dtype_ok(d.dtype) || d.out_dtype != d.dtype) return "ghost: out_dtype must equal dtype";
+    constexpr int kMaxChannels = 1 << 20, kMaxExtent = 1 << 24;
+    if (d.Cin <= 0 || d.Cin > kMaxChannels) return "ghost: channel count out of range (1 .. 2^20)";
+    if (d.groups != d.Cin || d.Cin != d.Cout) return "ghost: needs groups == Cin == Cout (the cheap convolution is depthwise)";
+    if (d.Cin % 4 != 0) return "ghost: the half width Cm must be a multiple of 4 channels";
+    if (d.kh != 3 || d.kw != 3) return "ghost: the cheap convolution's window must be 3x3";
+    if (d.stride_h != 1 || d.stride_w != 1) return "ghost: stride must be 1";
+    if (d.pad_t != 1 || d.pad_b != 1 || d.pad_l != 1 || d.pad_r != 1) return "ghost: padding must be 1 on every side";
+    if (d.dil_h != 1 || d.dil_w != 1) return "ghost: dilation unsupported";
+    if (d.post_act != PCV_ACT_NONE) return "ghost: post_act unsupported (nothing follows the skip add of GhostUnit)";
+    if (d.act < PCV_ACT_NONE || d.act > PCV_ACT_CLAMP01) return "ghost: unknown activation";
+    if (d.x_cpitch != round_up(d.Cin, 8)) return "ghost: x_cpitch must be Cm rounded up to a multiple of 8";
+    if (d.x_wpitch > 0 && d.x_wpitch != d.W) return "ghost: padded row pitch unsupported";
+    if (d.y_cpitch != 0 && d.y_cpitch != 2 * d.Cin) return "ghost: y_cpitch must be 0 or 2 Cm (y is dense)";
+    if (d.N > kMaxExtent || d.H > kMaxExtent || d.W > kMaxExtent) return "ghost: N / H / W out of range (> 2^24)";
+    if (d.N <= 0 || d.H <= 0 || d.W <= 0) return "ghost: empty input";
+    return nullptr;
+}
+
+int pcv_ghost_supported(const pcv_conv_desc* d) {
+    if (!d) { fail(nullptr, PCV_ERR_INVALID, "pcv_ghost_supported: NULL argument"); return 0; }
+    if (const char* why = check_ghost(*d)) { fail(nullptr, PCV_ERR_INVALID, std::string("pcv_ghost_supported: ") + why); return 0; }
+    return 1;
+}
+
+int pcv_ghost_dw_fused(pcv_ctx* ctx, const pcv_conv_desc* d, const void* m, const void* packed, const float* scale,
+                       const float* shift, const void* residual, void* y, void* stream) {
+    PCV_ENTER(ctx);
+    if (!d || !m || !packed || !y || !scale || !shift) return fail(ctx, PCV_ERR_INVALID, "pcv_ghost_dw_fused: NULL argument");
+    if (const char* why = check_ghost(*d)) return fail(ctx, PCV_ERR_INVALID, std::string("pcv_ghost_dw_fused: ") + why);
+    if (d->has_residual && !residual) return fail(ctx, PCV_ERR_INVALID, "pcv_ghost_dw_fused: has_residual but residual is NULL");
+    if (!aligned16(m) || !aligned16(packed) || !aligned16(y) || !aligned16(scale) || !aligned16(shift) ||
+        (d->has_residual && !aligned16(residual)))
+        return fail(ctx, PCV_ERR_INVALID, "pcv_ghost_dw_fused: pointers must be 16-byte aligned");
+    GhostParams p = {};
+    p.m = m;
+    p.w = packed;
+    p.res = d->has_residual ? residual : nullptr;
+    p.y = y;
+    p.scale = scale;
+    p.shift = shift;
+    p.ovf = ctx->ovf;
+    p.N = d->N; p.H = d->H; p.W = d->W;
+    p.Cm = d->Cin;
+    p.CP = d->x_cpitch;
+    p.C4 = d->Cin / 4;
+    // (factor by factor: N, H, W <= 2^24 and CP <= 2^20 each, their product does not fit 64 bits)
+    unsigned long long xbytes = (unsigned long long)d->N * d->H;
+    if (in_window(xbytes)) xbytes *= (unsigned long long)d->W;
+    if (in_window(xbytes)) xbytes *= (unsigned long long)p.CP * esize(d->dtype);
+    if (!in_window(xbytes)) return too_large(ctx, "pcv_ghost_dw_fused", "input");
+    p.x_bytes = (uint32_t)xbytes;
+    // rows per thread as pcv_dwconv2d_fused chooses them: whole columns when that still fills the chip, else shorter strips
+    const long cols = (long)d->N * p.W * p.C4;
+    const long want = (long)ctx->num_cu * 64 * 16;
+    int nseg = (int)((want + cols - 1) / cols);
+    if (nseg < 1) nseg = 1;
+    int TH = (p.H + nseg - 1) / nseg;
+    if (TH < 4) TH = p.H < 4 ? p.H : 4;
+    if (ctx->dw_th > 0) TH = ctx->dw_th < p.H ? ctx->dw_th : p.H;
+    p.TH = TH;
+    p.nseg = (p.H + TH - 1) / TH;
+    p.act = d->act;
+    p.total = cols * p.nseg;
+    p.flags = ctx->dw_flags;
+    unsigned grid = 0;
+    if (int rc = flat_grid(ctx, "pcv_ghost_dw_fused", p.total, &grid)) return rc;
+    const Kernel& K = kGhost[d->dtype == PCV_F32 ? 0 : (d->dtype == PCV_BF16 ? 1 : 2)][d->act <= PCV_ACT_RELU6 ? 1 : 0];
+    return launch(ctx, K, grid, (hipStream_t)stream, p);
 }
 
 static int pool_out(int in, int k, int s, int p, int ceil_mode) {

@@ -197,6 +197,7 @@ __device__ __forceinline__ float apply_act(float v, int act) {
         case PCV_ACT_SWISH: return v * __builtin_amdgcn_rcpf(1.f + __expf(-v));      // activ.py:20-21
         case PCV_ACT_HSIGMOID: return v != v ? v : fminf(fmaxf(v + 3.f, 0.f), 6.f) * (1.f / 6.f);      // activ.py:29-30
         case PCV_ACT_HSWISH: return v * fminf(fmaxf(v + 3.f, 0.f), 6.f) * (1.f / 6.f);    // activ.py:46-47
+        case PCV_ACT_CLAMP01: return v != v ? v : fminf(fmaxf(v, 0.f), 1.f);             // ghostnet.py:23-24 (NaN stays NaN, as in torch.clamp)
         default: return v;
     }
 }

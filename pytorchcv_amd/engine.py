@@ -5,7 +5,7 @@
 """
 
 __all__ = ['NHWC', 'DTYPES', 'default_dtype', 'set_compute_dtype', 'compute_dtype_of', 'Fp16Guard', 'fp16_overflow_count', 'from_nchw', 'to_nchw', 'ConvRunner',
-           'MixConvRunner', 'BnActRunner', 'IBNConvRunner', 'InstNormRunner', 'maxpool2d', 'avgpool2d', 'avgpool2d_pad', 'global_avgpool', 'se_excite', 'se_scale', 'se_forward', 'splat_forward', 'cbam_channel_gate', 'cbam_spatial', 'cbam_forward', 'channel_slice', 'cat_shuffle2', 'act_code',
+           'MixConvRunner', 'ghost_dw', 'BnActRunner', 'IBNConvRunner', 'InstNormRunner', 'maxpool2d', 'avgpool2d', 'avgpool2d_pad', 'global_avgpool', 'se_excite', 'se_scale', 'se_forward', 'splat_forward', 'cbam_channel_gate', 'cbam_spatial', 'cbam_forward', 'channel_slice', 'cat_shuffle2', 'act_code',
            'boundary', 'round8', 'channel_concat_into', 'interpolate', 'add', 'classify']
 
 import os
@@ -283,6 +283,9 @@ def act_code(activ) -> int:
         return 5
     if isinstance(activ, HSwish):
         return 6
+    from .models.ghostnet import GhostHSigmoid
+    if isinstance(activ, GhostHSigmoid):                 # clamp(x, 0, 1): PCV_ACT_CLAMP01 (pcv_se_excite / pcv_fc_f32 / pcv_ghost_dw_fused)
+        return 7
     raise NotImplementedError("activation {} has no fused MI355X epilogue yet".format(type(activ).__name__))
 
 
@@ -703,6 +706,47 @@ class MixConvRunner(ConvRunner):
             mid = (n0 + n1) // 2
             self._launch_range(x, d, None, y, n0, mid)
             self._launch_range(x, d, None, y, mid, n1)
+
+
+def ghost_dw(runner: ConvRunner, m: NHWC, act: int, residual: NHWC | None = None) -> NHWC:
+    """The second half of a ghost module as ONE launch (pcv_ghost_dw_fused; reference ghostnet.py:57-60 and, with `residual`, the
+    `x + identity` of ghostnet.py:167-174): y = cat((m, act(bn(dw3x3(m)))), channels) + residual, dense [N, H, W, 2 Cm].
+    `runner` is the plain depthwise ConvRunner of `cheap_conv` (its packed taps and folded BatchNorm are used as they are, at the
+    pitch round8(Cm)); `m` the main convolution's output with Cm logical channels. Shapes the kernel does not take raise
+    NotImplementedError with the library's text."""
+    _require_eval(runner)
+    c = runner.conv
+    Cm = c.out_channels
+    if not runner.depthwise or c.in_channels != Cm:
+        raise NotImplementedError("ghost module: the cheap convolution must be depthwise with as many outputs as inputs, got {}".format(c))
+    if not m.dense or m.C != Cm:
+        raise RuntimeError("ghost module: expected a dense handle of {} channels, got {} / pitch {} / row pitch {}".format(
+            Cm, m.C, m.cpitch, m.wpitch))
+    dp = runner.desc(m, act, 0, False)                  # the physical (round8) descriptor the taps and scale / shift are packed for
+    d = runner.desc(m, act, 0, residual is not None)
+    d.Cin = d.Cout = d.groups = Cm                      # the launch's: logical width, pitch round8(Cm)
+    d.y_cpitch = 2 * Cm
+    L = _lib.lib()
+    if not L.pcv_ghost_supported(ctypes.byref(d)):
+        raise NotImplementedError("ghost module ({} + {} channels on a {}x{} map) is not covered by the MI355X path: {}".format(
+            Cm, Cm, m.H, m.W, (L.pcv_last_error(None) or b"").decode()))
+    runner.prepare(m, dp)
+    if residual is not None:
+        if not residual.dense or tuple(residual.t.shape) != (m.N, m.H, m.W, 2 * Cm) or residual.dtype != m.dtype:
+            raise RuntimeError("residual shape/dtype mismatch: {} vs {}".format(tuple(residual.t.shape), (m.N, m.H, m.W, 2 * Cm)))
+    y = torch.empty((m.N, m.H, m.W, 2 * Cm), dtype=m.dtype, device=m.device)
+
+    def launch(n0, n1):                                 # images [n0, n1); halved when one launch would exceed the 2 GiB window
+        d.N = n1 - n0
+        rc = _call(m.device, "ghost_dw_fused", ctypes.byref(d), _ptr(m.t[n0:n1]), _ptr(runner.packed), _ptr(runner.scale),
+                   _ptr(runner.shift), _ptr(residual.t[n0:n1]) if residual is not None else None, _ptr(y[n0:n1]),
+                   accept=(_lib.PCV_ERR_TOO_LARGE,) if n1 - n0 > 1 else ())
+        if rc != 0:
+            mid = (n0 + n1) // 2
+            launch(n0, mid)
+            launch(mid, n1)
+    launch(0, m.N)
+    return NHWC(y, m.N, m.H, m.W, 2 * Cm, cpitch=2 * Cm)
 
 
 def _pool_out(n: int, k: int, s: int, p: int, ceil_mode: bool) -> int:

@@ -2,7 +2,7 @@
     `get_model(name, **kwargs)` with the reference's contract (pytorchcv/model_provider.py:1364-1382): case-insensitive
     name, `ValueError("Unsupported model: ...")` for unknown names, kwargs (`pretrained`, `root`, `in_channels`, `in_size`,
     `num_classes`) forwarded to the factory. The registry holds the families whose whole forward runs on the MI355X hot
-    path (ResNet, SE-ResNet, ResNeXt, SE-ResNeXt, MobileNet, MobileNetV2, MobileNetV3, EfficientNet, PreResNet, SE-PreResNet, DenseNet, ShuffleNetV2, VGG, ResNeSt(A), SKNet, CBAM-ResNet, MixNet, IBN-ResNet / IBN(b)-ResNet / IBN-ResNeXt).
+    path (ResNet, SE-ResNet, ResNeXt, SE-ResNeXt, MobileNet, MobileNetV2, MobileNetV3, EfficientNet, PreResNet, SE-PreResNet, DenseNet, ShuffleNetV2, VGG, ResNeSt(A), SKNet, CBAM-ResNet, MixNet, IBN-ResNet / IBN(b)-ResNet / IBN-ResNeXt, GhostNet).
 """
 
 __all__ = ['get_model']
@@ -27,6 +27,7 @@ from .models import mixnet as _mixnet
 from .models import ibnresnet as _ibnresnet
 from .models import ibnbresnet as _ibnbresnet
 from .models import ibnresnext as _ibnresnext
+from .models import ghostnet as _ghostnet
 
 _models = {}
 for _mod in (_resnet, _mobilenetv2, _resnext, _seresnet, _seresnext, _mobilenet, _mobilenetv3, _efficientnet, _preresnet, _sepreresnet, _densenet, _shufflenetv2, _vgg, _resnesta, _sknet):
@@ -44,11 +45,14 @@ _models_mixnet = {_name: getattr(_mixnet, _name) for _name in ("mixnet_s", "mixn
 # ... and a fourth: IBN-Net (InstanceNorm2d over the image in flight, tests/test_gpu_ibn.py)
 _models_ibn = {_name: getattr(_mod, _name) for _mod in (_ibnresnet, _ibnbresnet, _ibnresnext) for _name in _mod.__all__
                if _name.startswith(("ibn_res", "ibnb_res"))}
+# ... and a fifth: GhostNet (ghost modules: cheap convolution, concatenation and skip add in one launch, tests/test_gpu_ghostnet.py)
+_models_ghostnet = {"ghostnet": _ghostnet.ghostnet}
 
 
 def get_model(name, **kwargs):
     name = name.lower()
-    fn = _models.get(name) or _models_cbam.get(name) or _models_mixnet.get(name) or _models_ibn.get(name)
+    fn = _models.get(name) or _models_cbam.get(name) or _models_mixnet.get(name) or _models_ibn.get(name) or \
+        _models_ghostnet.get(name)
     if fn is None:
         raise ValueError("Unsupported model: {}".format(name))
     net = fn(**kwargs)

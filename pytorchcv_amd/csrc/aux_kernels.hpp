@@ -2,7 +2,6 @@
 // BN folding, max/avg pooling, SE squeeze / excite / scale. All NHWC, 8 channels (16 bytes at 16-bit) per thread.
 #pragma once
 #include "pcv_common.hpp"
-#include "dwconv.hpp"   // load8 / store8
 
 // ---- NCHW fp32 -> NHWC(cpitch, wpitch) --------------------------------------------------------------------
 // What `net(x)` receives in the reference (resnet.py:333) is NCHW fp32; the hot path is NHWC. One thread = one

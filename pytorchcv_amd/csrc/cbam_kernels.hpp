@@ -9,7 +9,6 @@
 // AdaptiveMaxPool2d and torch.max(dim); fmaxf would return the other operand and hide a NaN activation.
 #pragma once
 #include "pcv_common.hpp"
-#include "dwconv.hpp"   // load8 / store8
 
 // ---- ChannelGate pools (cbamresnet.py:64-65,72,74): spatial_mean_kernel's structure with a second running value ---------------
 // One 512-thread block per (image, group of <= 512 channel chunks), threads tile [rows x chunks], rows meet in LDS in row order: an

@@ -9,7 +9,7 @@
 //         y[.., c]      = m[.., c]                                       + res[.., c]           c in [0, Cm)
 //         y[.., Cm + c] = act(scale[c] * dw3x3(m)[.., c] + shift[c])     + res[.., Cm + c]
 //
-// HBM-bound like dwconv.hpp and built from its parts: one thread owns FOUR consecutive channels (Cm % 4 == 0 is all the net's widths
+// HBM-bound like dwconv.hpp and built from the same parts (dw_device.hpp: chunk loads, loadn / storen, packed fp32): one thread owns FOUR consecutive channels (Cm % 4 == 0 is all the net's widths
 // share: 12, 20, 36, 60, 92, 100 are no multiples of 8) of one column and walks down a strip of rows with the 3x3 fp32 window in
 // registers. Per row: one new input row through range-checked buffer loads (a tap outside the image is an offset beyond num_records
 // and reads zeros, no branches), requested three rows ahead; two stores, the window's centre (+ res) into [c, c + 4) and the cheap
@@ -17,7 +17,7 @@
 // case. Lanes run over channel chunks first, then columns: a wave's loads and each of its two store streams are contiguous NHWC spans.
 // Without res the main half is a bit copy of m for every finite value (16-bit -> fp32 -> 16-bit is exact).
 #pragma once
-#include "dwconv.hpp"
+#include "dw_device.hpp"
 
 struct GhostParams {
     const void* m;
@@ -38,21 +38,6 @@ struct GhostParams {
     uint32_t* ovf;        // the context's fp16 overflow counter (pcv_common.hpp, F16Guard)
 };
 
-// four consecutive elements from fp32 (8 bytes at 16 bit, 16 bytes fp32), optionally as a streaming store
-template <int DT> __device__ __forceinline__ void ghost_store4(void* base, size_t eidx, const float (&v)[4], bool nt) {
-    if constexpr (DT == PCV_F32) {
-        f32x4* q = reinterpret_cast<f32x4*>(reinterpret_cast<float*>(base) + eidx);
-        const f32x4 o = {v[0], v[1], v[2], v[3]};
-        if (nt) __builtin_nontemporal_store(o, q);
-        else *q = o;
-    } else {
-        u32x2* q = reinterpret_cast<u32x2*>(reinterpret_cast<uint16_t*>(base) + eidx);
-        const u32x2 o = {pack2<DT>(v[0], v[1]), pack2<DT>(v[2], v[3])};
-        if (nt) __builtin_nontemporal_store(o, q);
-        else *q = o;
-    }
-}
-
 // FAST: the cheap activation is none / relu / relu6 (dwconv.hpp)
 template <int DT, bool FAST>
 __global__ __launch_bounds__(256, 2) void ghost_dw_kernel(const GhostParams p) {
@@ -61,15 +46,8 @@ __global__ __launch_bounds__(256, 2) void ghost_dw_kernel(const GhostParams p) {
     constexpr int ES = Elem<DT>::BYTES;
     const long idx = (long)((p.flags & 2) ? blockIdx.x : xcd_remap(blockIdx.x, gridDim.x)) * 256 + threadIdx.x;      // (see dwconv_kernel)
     if (idx >= p.total) return;
-    const int c4 = (int)(idx % p.C4);
-    long t = idx / p.C4;
-    const int wo = (int)(t % p.W);
-    t /= p.W;
-    const int seg = (int)(t % p.nseg);
-    const int n = (int)(t / p.nseg);
-    const int c0 = c4 * CPT;
-    const int ho_begin = seg * p.TH;
-    const int ho_end = min(p.H, ho_begin + p.TH);
+    const DwThread th = dw_decode(idx, p.C4, p.W, p.nseg, p.TH, p.H);
+    const int n = th.n, wo = th.wo, c0 = th.chunk * CPT, ho_begin = th.ho_begin, ho_end = th.ho_end;
 
     const __amdgpu_buffer_rsrc_t xrsrc = buffer_rsrc(p.m, p.x_bytes);
 
@@ -95,7 +73,7 @@ __global__ __launch_bounds__(256, 2) void ghost_dw_kernel(const GhostParams p) {
     uint32_t coloff[KS];
 #pragma unroll
     for (int q = 0; q < KS; ++q)
-        coloff[q] = (unsigned)(wo - 1 + q) < (unsigned)p.W ? (uint32_t)(((wo - 1 + q) * p.CP + c0) * ES) : 0x80000000u;
+        coloff[q] = (unsigned)(wo - 1 + q) < (unsigned)p.W ? (uint32_t)(((wo - 1 + q) * p.CP + c0) * ES) : kOutOfRange;
     const uint32_t rowbytes = (uint32_t)(p.W * p.CP * ES);
     const uint32_t imgoff = (uint32_t)n * (uint32_t)p.H * rowbytes;
 
@@ -104,7 +82,7 @@ __global__ __launch_bounds__(256, 2) void ghost_dw_kernel(const GhostParams p) {
         const uint32_t rbase = imgoff + (uint32_t)hi * rowbytes;
 #pragma unroll
         for (int q = 0; q < KS; ++q) {
-            const uint32_t off = (rowok && coloff[q] != 0x80000000u) ? rbase + coloff[q] : 0x80000000u;
+            const uint32_t off = (rowok && coloff[q] != kOutOfRange) ? rbase + coloff[q] : kOutOfRange;
             raw_load<DT, CPT>(xrsrc, off, row[q]);
         }
     };
@@ -165,7 +143,7 @@ __global__ __launch_bounds__(256, 2) void ghost_dw_kernel(const GhostParams p) {
                     u[2 * e] = ctr[0];
                     u[2 * e + 1] = ctr[1];
                 }
-                if constexpr (FAST) clampn(v, act); else apply_actn(v, act);
+                dw_act<FAST>(v, act);
                 if (has_res) {
                     float r4[CPT], s4[CPT];
                     loadn<DT, CPT>(p.res, eoff, r4);
@@ -175,8 +153,9 @@ __global__ __launch_bounds__(256, 2) void ghost_dw_kernel(const GhostParams p) {
                     guard.see(u);                                        // (without res the main half stores what m already held)
                 }
                 if (!bounded) guard.see(v);
-                ghost_store4<DT>(p.y, eoff, u, nt);
-                ghost_store4<DT>(p.y, eoff + p.Cm, v, nt);
+                // (dw_flags bit 0 reaches both 4-channel stores here, at every width - unlike the 5x5 and MixConv stores: kept)
+                storen<DT, CPT>(p.y, eoff, u, nt);
+                storen<DT, CPT>(p.y, eoff + p.Cm, v, nt);
                 ++ho;
             }
         });

@@ -7,7 +7,6 @@
 //   instnorm_apply_kernel  y = act(x * a + b)  - bn_act_kernel with per-(image, channel) coefficients
 #pragma once
 #include "pcv_common.hpp"
-#include "dwconv.hpp"   // load8 / store8
 
 constexpr int kInGroup = 8;        // 8-channel chunks per statistics block: 64 channels, one 128-byte line per pixel at 16 bit
 constexpr int kInThreads = 512;

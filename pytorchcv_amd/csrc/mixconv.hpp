@@ -37,8 +37,9 @@
 // Packed blob: per class, from a 16-byte aligned offset, the taps [KS * KS][span] in the storage type (span = channels of the region).
 //
 // Loads are buffer loads with range checking: a padded tap is an offset beyond num_records and returns zeros, no branches.
+// The chunk types, loadn / storen and the packed-fp32 helpers are dw_device.hpp's; the streaming loop is dw_stream_rows, shared with dwconv5_kernel.
 #pragma once
-#include "dwconv.hpp"
+#include "dw_device.hpp"
 
 constexpr int kMixMaxGroups = 5;
 
@@ -126,221 +127,19 @@ __global__ __launch_bounds__(256) void pack_mix_kernel(const MixPackParams p) {
     store_elem<DT>(static_cast<char*>(p.out) + p.woff[g], (size_t)r, v);
 }
 
-// CPT channels as they come from memory (CPT = 4: 8 B at 16 bit / 16 B fp32; CPT = 2: 4 B / 8 B)
-template <int ND> struct MixRawVec;
-template <> struct MixRawVec<4> { u32x4 q; __device__ __forceinline__ uint32_t get(int i) const { return q[i]; } };
-template <> struct MixRawVec<2> { u32x2 q; __device__ __forceinline__ uint32_t get(int i) const { return q[i]; } };
-template <> struct MixRawVec<1> { uint32_t q; __device__ __forceinline__ uint32_t get(int) const { return q; } };
-template <int DT, int CPT> struct MixRaw : MixRawVec<(DT == PCV_F32 ? CPT : CPT / 2)> {};
-
-#if defined(__HIP_DEVICE_COMPILE__)
-template <int DT, int CPT>
-__device__ __forceinline__ void mix_raw_load(const __amdgpu_buffer_rsrc_t& rsrc, uint32_t off, MixRaw<DT, CPT>& r) {
-    constexpr int ND = DT == PCV_F32 ? CPT : CPT / 2;
-    if constexpr (ND == 4) r.q = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 0);
-    else if constexpr (ND == 2) r.q = __builtin_amdgcn_raw_buffer_load_b64(rsrc, off, 0, 0);
-    else r.q = __builtin_amdgcn_raw_buffer_load_b32(rsrc, off, 0, 0);
-}
-#endif
-template <int DT, int CPT> __device__ __forceinline__ void mix_raw_to_f32x2(const MixRaw<DT, CPT>& r, f32x2 (&v)[CPT / 2]) {
-#pragma unroll
-    for (int e = 0; e < CPT / 2; ++e) {
-        if constexpr (DT == PCV_F32) {
-            v[e] = (f32x2){__uint_as_float(r.get(2 * e)), __uint_as_float(r.get(2 * e + 1))};
-        } else {
-            float lo, hi;
-            unpack2<DT>(r.get(e), lo, hi);
-            v[e] = (f32x2){lo, hi};
-        }
-    }
-}
-// CPT consecutive elements at a plain pointer as fp32 pairs / back (taps, scale, shift, output)
-template <int DT, int CPT> __device__ __forceinline__ void mix_load(const void* base, size_t eidx, f32x2 (&v)[CPT / 2]) {
-    MixRaw<DT, CPT> r;
-    typedef decltype(r.q) vec;
-    r.q = *reinterpret_cast<const vec*>(static_cast<const char*>(base) + eidx * Elem<DT>::BYTES);
-    mix_raw_to_f32x2<DT, CPT>(r, v);
-}
-template <int DT, int CPT> __device__ __forceinline__ void mix_store(void* base, size_t eidx, const float (&v)[CPT], bool nt) {
-    if constexpr (CPT == 4) {
-        storen<DT, 4>(base, eidx, v, nt);
-    } else if constexpr (DT == PCV_F32) {
-        *reinterpret_cast<f32x2*>(reinterpret_cast<float*>(base) + eidx) = (f32x2){v[0], v[1]};
-    } else {
-        *reinterpret_cast<uint32_t*>(reinterpret_cast<uint16_t*>(base) + eidx) = pack2<DT>(v[0], v[1]);
-    }
-}
-
-// one window class: KS x KS over the chunks of class G_IDX = (KS - 3) / 2; `blk` counts from the first block of the class
+// one window class: KS x KS over the chunks of class GI = (KS - 3) / 2; `blk` counts from the first block of the class
 template <int DT, int KS, int S, bool FAST, int CPT>
 __device__ __forceinline__ void mixdw_class(const MixParams& p, const uint32_t blk) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    constexpr int GI = (KS - 3) / 2, NV = CPT / 2;
-    constexpr int ES = Elem<DT>::BYTES;
-    constexpr int NSLOT = (KS + S - 1) / S;        // output rows in flight
-    constexpr int PERIOD = S * NSLOT;              // input rows after which the (phase -> slot) pattern repeats
+    constexpr int GI = (KS - 3) / 2;
     const int nchunk = p.nchunk[GI];
     const long idx = (long)blk * 256 + threadIdx.x;
     if (idx >= (long)p.N * p.nseg * p.Wo * nchunk) return;
-    const int ch = (int)(idx % nchunk);
-    long t0 = idx / nchunk;
-    const int wo = (int)(t0 % p.Wo);
-    t0 /= p.Wo;
-    const int seg = (int)(t0 % p.nseg);
-    const int n = (int)(t0 / p.nseg);
-    const int cr = ch * CPT;                       // channel within the class region
-    const int c0 = p.cbeg[GI] + cr;
-    const int ho_begin = seg * p.TH;
-    const int nrows = min(p.Ho, ho_begin + p.TH) - ho_begin;
-
-    const __amdgpu_buffer_rsrc_t xrsrc = buffer_rsrc(p.x, p.x_bytes);
-
-    constexpr bool WREG = KS <= 7;                 // taps resident in registers (else: fetched per filter row, see the header comment)
-    const char* wbase = static_cast<const char*>(p.w) + p.woff[GI];
-    const int span = p.span[GI];
-    f32x2 wgt[WREG ? KS * KS : 1][NV];
-    if constexpr (WREG) {
-#pragma unroll
-        for (int k = 0; k < KS * KS; ++k) mix_load<DT, CPT>(wbase, (size_t)k * span + cr, wgt[k]);
-    }
-    // 9 x 9 / 11 x 11 at 16 bit: the taps stay resident too, but as they are stored - one dword per pair - and are unpacked on use
-    constexpr bool WPK = !WREG && DT != PCV_F32;
-    uint32_t wpk[WPK ? KS * KS : 1];
-    if constexpr (WPK) {
-        static_assert(CPT == 2, "one dword per tap");
-#pragma unroll
-        for (int k = 0; k < KS * KS; ++k) wpk[k] = *reinterpret_cast<const uint32_t*>(wbase + ((size_t)k * span + cr) * ES);
-    }
-    f32x2 sc[NV], sf[NV];
-    mix_load<PCV_F32, CPT>(p.scale, c0, sc);
-    mix_load<PCV_F32, CPT>(p.shift, c0, sf);
-    const ActClamp act = make_act(p.act);
-    F16Guard<DT> guard;
-    const bool bounded = act_bounded(p.act);
-
-    const int wi0 = wo * S - KS / 2;
-    uint32_t coloff[KS];
-#pragma unroll
-    for (int q = 0; q < KS; ++q)
-        coloff[q] = (unsigned)(wi0 + q) < (unsigned)p.W ? (uint32_t)(((wi0 + q) * p.C + c0) * ES) : kOutOfRange;
-    const uint32_t rowbytes = (uint32_t)(p.W * p.C * ES);
-    const uint32_t imgoff = (uint32_t)n * (uint32_t)p.H * rowbytes;
-    auto fetch_row = [&](int hi, bool need, MixRaw<DT, CPT> (&row)[KS]) {
-        const bool rowok = need && (unsigned)hi < (unsigned)p.H;
-        const uint32_t rbase = imgoff + (uint32_t)hi * rowbytes;
-#pragma unroll
-        for (int q = 0; q < KS; ++q)
-            mix_raw_load<DT, CPT>(xrsrc, (rowok && coloff[q] != kOutOfRange) ? rbase + coloff[q] : kOutOfRange, row[q]);
-    };
-
-    f32x2 acc[NSLOT][NV];
-#pragma unroll
-    for (int s = 0; s < NSLOT; ++s)
-#pragma unroll
-        for (int e = 0; e < NV; ++e) acc[s][e] = (f32x2){0.f, 0.f};
-
-    const int hi_first = ho_begin * S - KS / 2;
-    const int nsteps = (nrows - 1) * S + KS;       // input rows this strip touches
-    // the row of step t sits in ring[t % PERIOD]; the row PD steps ahead is requested into its own (static) slot (see dwconv5_kernel)
-    // (the 9 x 9 and 11 x 11 classes keep two rows only - the current one and the next, handed over by register copies: a ring of
-    // PERIOD static slots stays live as a whole across the conditional phases, 264 registers for 11 x 11 at fp32, and their ~100
-    // packed FMAs per step cover the one row of latency that the copy leaves)
-    constexpr int PD = WREG ? 2 : 1;
-    MixRaw<DT, CPT> ring[WREG ? PERIOD : 2][KS];
-    if constexpr (WREG) {
-#pragma unroll
-        for (int d = 0; d < PD; ++d) fetch_row(hi_first + d, d < nsteps, ring[d]);
-    } else {
-        fetch_row(hi_first, true, ring[1]);
-    }
-    int t = 0;
-    while (t < nsteps) {
-        static_for<PERIOD>([&](auto PHC) {
-            constexpr int PH = decltype(PHC)::value;
-            if (t < nsteps) {
-                constexpr int CUR = WREG ? PH : 0;
-                if constexpr (WREG) {
-                    fetch_row(hi_first + t + PD, t + PD < nsteps, ring[(PH + PD) % PERIOD]);
-                } else {
-#pragma unroll
-                    for (int q = 0; q < KS; ++q) ring[0][q] = ring[1][q];
-                    fetch_row(hi_first + t + 1, t + 1 < nsteps, ring[1]);
-                }
-                f32x2 xv[KS][NV];
-#pragma unroll
-                for (int q = 0; q < KS; ++q) mix_raw_to_f32x2<DT, CPT>(ring[CUR][q], xv[q]);
-#pragma unroll
-                for (int dy = 0; dy < KS; ++dy) {
-                    const int d = PH - dy;                                 // S * (output row), modulo the unroll period
-                    if (S == 1 || (d & 1) == 0) {                          // stride 2: this input row only meets every other filter row
-                        const int slot = (((S == 1 ? d : d / 2) % NSLOT) + NSLOT) % NSLOT;
-                        if (t - dy >= 0) {
-                            if constexpr (WREG) {
-#pragma unroll
-                                for (int q = 0; q < KS; ++q)
-#pragma unroll
-                                    for (int e = 0; e < NV; ++e) pk_fma_acc(acc[slot][e], xv[q][e], wgt[dy * KS + q][e]);
-                            } else if constexpr (WPK) {
-#pragma unroll
-                                for (int q = 0; q < KS; ++q) {
-                                    // (a copy the compiler cannot see through: the unpacked pair is loop-invariant, and hoisted out
-                                    // of the row loop the pairs would take the 2 x KS x KS registers this form exists to save)
-                                    uint32_t wv = wpk[dy * KS + q];
-                                    asm volatile("" : "+v"(wv));
-                                    float lo, hi;
-                                    unpack2<DT>(wv, lo, hi);
-                                    const f32x2 w2 = {lo, hi};
-                                    pk_fma_acc(acc[slot][0], xv[q][0], w2);
-                                }
-                            } else {
-                                // (the offset is made opaque per step: the taps are loop-invariant, and hoisted out of the row loop
-                                // they would all be live at once again - the registers this form exists to save)
-                                uint32_t wcol = (uint32_t)cr;
-                                asm volatile("" : "+v"(wcol));
-                                f32x2 wrow[KS][NV];
-#pragma unroll
-                                for (int q = 0; q < KS; ++q) mix_load<DT, CPT>(wbase, (size_t)(dy * KS + q) * span + wcol, wrow[q]);
-#pragma unroll
-                                for (int q = 0; q < KS; ++q)
-#pragma unroll
-                                    for (int e = 0; e < NV; ++e) pk_fma_acc(acc[slot][e], xv[q][e], wrow[q][e]);
-                                __builtin_amdgcn_sched_barrier(0);      // one filter row of taps in flight, not all the step's
-                            }
-                        }
-                    }
-                }
-                // the output row whose last filter row (dy = KS - 1) was this input row is complete
-                {
-                    const int d = PH - (KS - 1);
-                    if (S == 1 || (d & 1) == 0) {
-                        const int slot = (((S == 1 ? d : d / 2) % NSLOT) + NSLOT) % NSLOT;
-                        const int o2 = t - (KS - 1);
-                        if (o2 >= 0) {
-                            const int o = o2 / S;
-                            if (o < nrows) {
-                                const size_t eoff = (((size_t)n * p.Ho + ho_begin + o) * p.Wo + wo) * p.C + c0;
-                                float v[CPT];
-#pragma unroll
-                                for (int e = 0; e < NV; ++e) {
-                                    f32x2 t2 = sf[e];
-                                    pk_fma_acc(t2, acc[slot][e], sc[e]);
-                                    v[2 * e] = t2[0];
-                                    v[2 * e + 1] = t2[1];
-                                }
-                                if constexpr (FAST) clampn(v, act); else apply_actn(v, act);
-                                if (!bounded) guard.see(v);
-                                mix_store<DT, CPT>(p.y, eoff, v, (p.flags & 1) != 0);
-                            }
-#pragma unroll
-                            for (int e = 0; e < NV; ++e) acc[slot][e] = (f32x2){0.f, 0.f};
-                        }
-                    }
-                }
-                ++t;
-            }
-        });
-    }
-    guard.commit(p.ovf);
+    const DwThread th = dw_decode(idx, nchunk, p.Wo, p.nseg, p.TH, p.Ho);
+    const int cr = th.chunk * CPT;                 // channel within the class region
+    const DwStream a = {p.x, p.x_bytes, static_cast<const char*>(p.w) + p.woff[GI], p.span[GI], cr, p.scale, p.shift, nullptr, p.y,
+                        p.H, p.W, p.C, p.Ho, p.Wo, KS / 2, KS / 2, p.act, PCV_ACT_NONE, p.ovf};
+    dw_stream_rows<DT, KS, S, FAST, CPT, false>(a, th, p.cbeg[GI] + cr);
 #endif  // __HIP_DEVICE_COMPILE__
 }
 

@@ -742,6 +742,17 @@ static MbLds mbconv_plan(int stride, bool expand, int ka, int nChunks, int nRowT
     return two;
 }
 
+// index of a storage type in the depthwise tables below
+static int dt_index(int dtype) { return dtype == PCV_F32 ? 0 : (dtype == PCV_BF16 ? 1 : 2); }
+
+// depthwise 3x3 / 5x5 (dwconv.hpp): [storage type][3x3 s1, 3x3 s2, 5x5 s1, 5x5 s2][clamp-only activations]; no dynamic LDS
+#define DW_TYPE(DT)                                                                                                            \
+    {{kernel_of(dwconv_kernel<DT, 3, 1, false>, 256, 0), kernel_of(dwconv_kernel<DT, 3, 1, true>, 256, 0)},                    \
+     {kernel_of(dwconv_kernel<DT, 3, 2, false>, 256, 0), kernel_of(dwconv_kernel<DT, 3, 2, true>, 256, 0)},                    \
+     {kernel_of(dwconv5_kernel<DT, 1, false>, 256, 0), kernel_of(dwconv5_kernel<DT, 1, true>, 256, 0)},                        \
+     {kernel_of(dwconv5_kernel<DT, 2, false>, 256, 0), kernel_of(dwconv5_kernel<DT, 2, true>, 256, 0)}}
+static const Kernel kDw[3][4][2] = {DW_TYPE(PCV_F32), DW_TYPE(PCV_BF16), DW_TYPE(PCV_F16)};
+
 // depthwise MixConv (mixconv.hpp): [storage type][stride - 1][clamp-only activation][kernels - 2]; no dynamic LDS
 #define MIX_KERNEL(DT, S, FAST, G) kernel_of(mixdw_kernel<DT, S, FAST, G>, 256, 0)
 #define MIX_ROW(DT, S, FAST) {MIX_KERNEL(DT, S, FAST, 2), MIX_KERNEL(DT, S, FAST, 3), MIX_KERNEL(DT, S, FAST, 4), MIX_KERNEL(DT, S, FAST, 5)}
@@ -876,18 +887,6 @@ static const char* mbconv_unsupported(const pcv_conv_desc* de, const pcv_conv_de
 }
 
 // launch helpers (templates need C++ linkage)
-template <int DT, bool FAST> static void launch_dw2(const pcv_conv_desc& d, const DwParams& p, unsigned grid, hipStream_t s) {
-    if (d.kh == 3 && d.stride_h == 1) dwconv_kernel<DT, 3, 1, FAST><<<grid, 256, 0, s>>>(p);
-    else if (d.kh == 3) dwconv_kernel<DT, 3, 2, FAST><<<grid, 256, 0, s>>>(p);
-    else if (d.stride_h == 1) dwconv5_kernel<DT, 1, FAST><<<grid, 256, 0, s>>>(p);     // 5x5: row streaming, 4 channels per thread
-    else dwconv5_kernel<DT, 2, FAST><<<grid, 256, 0, s>>>(p);
-}
-static void launch_dw(const pcv_conv_desc& d, const DwParams& p, unsigned grid, hipStream_t s) {
-    for_dtype(d.dtype, [&](auto T) {
-        if (d.act <= PCV_ACT_RELU6 && d.post_act <= PCV_ACT_RELU6) launch_dw2<DT_OF(T), true>(d, p, grid, s);
-        else launch_dw2<DT_OF(T), false>(d, p, grid, s);
-    });
-}
 // `dt` -> `ot` (dt or fp32); `radix` > 1: the split-attention squeeze over x with radix * C channels per pixel (pcv_splat_squeeze)
 static void launch_mean(const void* x, void* y, int N, int HW, int C, int dt, int ot, hipStream_t s, int radix = 1) {
     dim3 grid((unsigned)N, (unsigned)((C / 8 + 511) / 512));
@@ -1767,6 +1766,19 @@ int pcv_conv2d_nchw_stem_fused(pcv_ctx* ctx, const pcv_conv_desc* d, const float
     return conv2d_impl(ctx, d, x_nchw, packed, scale, shift, nullptr, y, stream, pool != 0, nullptr, true);
 }
 
+// Rows per thread of the depthwise launches (`cols` columns of channel chunks, Ho output rows): the whole column when that still
+// fills the chip (>= ~16 waves per CU), else shorter strips of at least 4 rows; the dw_th tuning overrides the choice.
+static void dw_strips(const pcv_ctx* ctx, int Ho, long cols, int* TH_out, int* nseg_out) {
+    const long want = (long)ctx->num_cu * 64 * 16;
+    int nseg = (int)((want + cols - 1) / cols);
+    if (nseg < 1) nseg = 1;
+    int TH = (Ho + nseg - 1) / nseg;
+    if (TH < 4) TH = Ho < 4 ? Ho : 4;
+    if (ctx->dw_th > 0) TH = ctx->dw_th < Ho ? ctx->dw_th : Ho;
+    *TH_out = TH;
+    *nseg_out = (Ho + TH - 1) / TH;
+}
+
 int pcv_dwconv2d_fused(pcv_ctx* ctx, const pcv_conv_desc* d, const void* x, const void* packed, const float* scale,
                        const float* shift, const void* residual, void* y, void* stream) {
     PCV_ENTER(ctx);
@@ -1795,24 +1807,16 @@ int pcv_dwconv2d_fused(pcv_ctx* ctx, const pcv_conv_desc* d, const void* x, cons
     if (p.Ho <= 0 || p.Wo <= 0) return fail(ctx, PCV_ERR_INVALID, "pcv_dwconv2d_fused: empty output");
     p.pt = d->pad_t; p.pl = d->pad_l;
     p.C8 = d->Cin / (d->kh == 5 ? 4 : 8);          // channel chunks per pixel (5x5 runs 4 channels per thread)
-    // rows per thread: whole column when that still fills the chip (>= ~16 waves per CU), else shorter strips
     const long cols = (long)d->N * p.Wo * p.C8;
-    const long want = (long)ctx->num_cu * 64 * 16;
-    int nseg = (int)((want + cols - 1) / cols);
-    if (nseg < 1) nseg = 1;
-    int TH = (p.Ho + nseg - 1) / nseg;
-    if (TH < 4) TH = p.Ho < 4 ? p.Ho : 4;
-    if (ctx->dw_th > 0) TH = ctx->dw_th < p.Ho ? ctx->dw_th : p.Ho;
-    p.TH = TH;
-    p.nseg = (p.Ho + TH - 1) / TH;
+    dw_strips(ctx, p.Ho, cols, &p.TH, &p.nseg);
     p.act = d->act;
     p.post_act = d->post_act;
     p.total = cols * p.nseg;
     p.flags = ctx->dw_flags;
     unsigned grid = 0;
     if (int rc = flat_grid(ctx, "pcv_dwconv2d_fused", p.total, &grid)) return rc;
-    launch_dw(*d, p, grid, (hipStream_t)stream);
-    return launched(ctx);
+    const Kernel& K = kDw[dt_index(d->dtype)][(d->kh == 3 ? 0 : 2) + d->stride_h - 1][d->act <= PCV_ACT_RELU6 && d->post_act <= PCV_ACT_RELU6 ? 1 : 0];
+    return launch(ctx, K, grid, (hipStream_t)stream, p);
 }
 
 // ---- depthwise MixConv (mixconv.hpp) ---------------------------------------------------------------------------------------------
@@ -1898,16 +1902,7 @@ int pcv_mixconv2d_fused(pcv_ctx* ctx, const pcv_conv_desc* d, const int* kernels
     p.x_bytes = (uint32_t)xbytes;
     p.Ho = (d->H - 1) / d->stride_h + 1;           // pad k / 2 on both sides: the same for every window of the list
     p.Wo = (d->W - 1) / d->stride_w + 1;
-    // rows per thread as pcv_dwconv2d_fused chooses them, from the columns of 4-channel chunks
-    const long cols = (long)d->N * p.Wo * (d->Cin / 4);
-    const long want = (long)ctx->num_cu * 64 * 16;
-    int nseg = (int)((want + cols - 1) / cols);
-    if (nseg < 1) nseg = 1;
-    int TH = (p.Ho + nseg - 1) / nseg;
-    if (TH < 4) TH = p.Ho < 4 ? p.Ho : 4;
-    if (ctx->dw_th > 0) TH = ctx->dw_th < p.Ho ? ctx->dw_th : p.Ho;
-    p.TH = TH;
-    p.nseg = (p.Ho + TH - 1) / TH;
+    dw_strips(ctx, p.Ho, (long)d->N * p.Wo * (d->Cin / 4), &p.TH, &p.nseg);          // (columns of 4-channel chunks)
     p.act = d->act;
     p.flags = ctx->dw_flags;
     long long blocks = 0;
@@ -1922,7 +1917,7 @@ int pcv_mixconv2d_fused(pcv_ctx* ctx, const pcv_conv_desc* d, const int* kernels
         if (blocks > 0x7fffffffll) return too_large(ctx, "pcv_mixconv2d_fused", "the grid");
         p.blk_end[g] = (uint32_t)blocks;
     }
-    const Kernel& K = kMix[d->dtype == PCV_F32 ? 0 : (d->dtype == PCV_BF16 ? 1 : 2)][d->stride_h - 1][d->act <= PCV_ACT_RELU6 ? 1 : 0][nk - 2];
+    const Kernel& K = kMix[dt_index(d->dtype)][d->stride_h - 1][d->act <= PCV_ACT_RELU6 ? 1 : 0][nk - 2];
     return launch(ctx, K, (unsigned)blocks, (hipStream_t)stream, p);
 }
 
@@ -1982,22 +1977,14 @@ int pcv_ghost_dw_fused(pcv_ctx* ctx, const pcv_conv_desc* d, const void* m, cons
     if (in_window(xbytes)) xbytes *= (unsigned long long)p.CP * esize(d->dtype);
     if (!in_window(xbytes)) return too_large(ctx, "pcv_ghost_dw_fused", "input");
     p.x_bytes = (uint32_t)xbytes;
-    // rows per thread as pcv_dwconv2d_fused chooses them: whole columns when that still fills the chip, else shorter strips
     const long cols = (long)d->N * p.W * p.C4;
-    const long want = (long)ctx->num_cu * 64 * 16;
-    int nseg = (int)((want + cols - 1) / cols);
-    if (nseg < 1) nseg = 1;
-    int TH = (p.H + nseg - 1) / nseg;
-    if (TH < 4) TH = p.H < 4 ? p.H : 4;
-    if (ctx->dw_th > 0) TH = ctx->dw_th < p.H ? ctx->dw_th : p.H;
-    p.TH = TH;
-    p.nseg = (p.H + TH - 1) / TH;
+    dw_strips(ctx, p.H, cols, &p.TH, &p.nseg);
     p.act = d->act;
     p.total = cols * p.nseg;
     p.flags = ctx->dw_flags;
     unsigned grid = 0;
     if (int rc = flat_grid(ctx, "pcv_ghost_dw_fused", p.total, &grid)) return rc;
-    const Kernel& K = kGhost[d->dtype == PCV_F32 ? 0 : (d->dtype == PCV_BF16 ? 1 : 2)][d->act <= PCV_ACT_RELU6 ? 1 : 0];
+    const Kernel& K = kGhost[dt_index(d->dtype)][d->act <= PCV_ACT_RELU6 ? 1 : 0];
     return launch(ctx, K, grid, (hipStream_t)stream, p);
 }
 

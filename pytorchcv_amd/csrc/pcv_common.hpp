@@ -308,3 +308,32 @@ __device__ __forceinline__ uint32_t xcd_remap(uint32_t b, uint32_t nwg) {
     const uint32_t start = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
     return start + idx;
 }
+
+// eight consecutive elements at a plain pointer as fp32 and back (the element-wise kernels, the 8-channel depthwise chunks)
+template <int DT> __device__ __forceinline__ void load8(const void* base, size_t eidx, float (&v)[8]) {
+    if constexpr (DT == PCV_F32) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(base) + eidx);
+        const f32x4 b = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(base) + eidx + 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { v[e] = a[e]; v[4 + e] = b[e]; }
+    } else {
+        const u32x4 r = *reinterpret_cast<const u32x4*>(reinterpret_cast<const uint16_t*>(base) + eidx);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) unpack2<DT>(r[e], v[2 * e], v[2 * e + 1]);
+    }
+}
+// (nt: a launch-uniform streaming store - the line is not kept for a reader that never comes; fp32 stores never took it)
+template <int DT> __device__ __forceinline__ void store8(void* base, size_t eidx, const float (&v)[8], bool nt = false) {
+    if constexpr (DT == PCV_F32) {
+        float* p = reinterpret_cast<float*>(base) + eidx;
+        *reinterpret_cast<f32x4*>(p) = (f32x4){v[0], v[1], v[2], v[3]};
+        *reinterpret_cast<f32x4*>(p + 4) = (f32x4){v[4], v[5], v[6], v[7]};
+    } else {
+        u32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = pack2<DT>(v[2 * e], v[2 * e + 1]);
+        u32x4* q = reinterpret_cast<u32x4*>(reinterpret_cast<uint16_t*>(base) + eidx);
+        if (nt) __builtin_nontemporal_store(o, q);
+        else *q = o;
+    }
+}

@@ -20,7 +20,7 @@ def _table():
 
 
 def test_depthwise_table_reaches_all_24_instances():
-    """dispatch rule of launch_dw: act <= RELU6 and post_act <= RELU6 -> FAST; {3, 5} x stride {1, 2} x FAST x 3 dtypes"""
+    """FAST index of the kDw table: act <= RELU6 and post_act <= RELU6 -> FAST; {3, 5} x stride {1, 2} x FAST x 3 dtypes"""
     reached = {(ks, s, fast, dt) for (ks, s, fast, dt, _, _, _) in _table()}
     assert reached == set(DW_INSTANCES) and len(reached) == 24
 

@@ -211,7 +211,7 @@ def dw_cases(ks, s, fast):
 
 
 def is_fast(act, post):
-    """the dispatch rule of launch_dw (csrc/pcv_api.hip): both activations clamps -> the FAST build"""
+    """the FAST index of the kDw table (pcv_dwconv2d_fused, csrc/pcv_api.hip): both activations clamps -> the FAST build"""
     return act <= RELU6 and post <= RELU6
 
 

@@ -17,6 +17,9 @@ Shapes (N, C, kernels, stride, H, W):
   (2, 48, 3, 1, 40, 3)     tall map: more than one row strip per column
   (2, 1200, 4, 1, 7, 7)    300-wide groups
   (2, 240, 4, 2, 5, 5)     60-wide groups at stride 2
+  (2, 24, 5, 1, 7, 5)      five kernels at stride 1 on the narrowest list the plan takes (groups of 8, 4, 4, 4, 4): the 11x11 window
+                           overhangs the whole map, the strips do not divide 7 rows
+  (2, 8, 2, 2, 7, 5)       two kernels at stride 2 on 8 channels: ragged last row and column
 """
 
 import ctypes
@@ -31,7 +34,8 @@ from mixconv_ref import mix_operands, mix_ref, out_bound, taps_from_blob, taps_o
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(2, 360, 4, 1, 9, 11), (2, 720, 5, 2, 9, 10), (2, 720, 5, 2, 14, 14), (3, 144, 3, 2, 15, 16), (2, 240, 2, 1, 12, 7),
-          (2, 16, 2, 1, 1, 1), (2, 48, 3, 1, 40, 3), (2, 1200, 4, 1, 7, 7), (2, 240, 4, 2, 5, 5)]
+          (2, 16, 2, 1, 1, 1), (2, 48, 3, 1, 40, 3), (2, 1200, 4, 1, 7, 7), (2, 240, 4, 2, 5, 5), (2, 24, 5, 1, 7, 5),
+          (2, 8, 2, 2, 7, 5)]
 DTYPES = ["fp32", "bf16", "fp16"]
 OTHER_CODES = (NONE, RELU6, SIGMOID, HSIGMOID, HSWISH)         # every code besides the two the nets use
 

@@ -38,7 +38,7 @@ extern "C" {
  *    likewise + pcv_classify_f32, + pcv_cbam_pool / _excite / _spatial_pool / _apply,
  *    + pcv_mixconv_packed_bytes / pcv_mixconv_pack / pcv_mixconv2d_fused, + pcv_bottleneck_supported / pcv_bottleneck_fused,
  *    + pcv_instnorm_workspace_bytes / pcv_instnorm_act, + pcv_ghost_supported / pcv_ghost_dw_fused and the activation code
- *    PCV_ACT_CLAMP01) */
+ *    PCV_ACT_CLAMP01, + pcv_hr_fuse_supported / pcv_hr_fuse) */
 #define PCV_ABI_VERSION 5
 
 typedef struct pcv_ctx pcv_ctx;
@@ -296,6 +296,24 @@ int pcv_channel_concat(pcv_ctx* ctx, const void* x, void* y, long rows, int C, i
  * mode "bilinear" with the given align_corners, else mode "nearest". fp32 arithmetic, ATen's source-coordinate rules. */
 int pcv_interpolate(pcv_ctx* ctx, const void* x, void* y, int N, int H, int W, int C, int Ho, int Wo, int bilinear,
                     int align_corners, int dtype, void* stream);
+/* HRNet's multi-resolution exchange for one output branch as ONE launch: the sum over the branches at the end of HRBlock.forward
+ * (hrnet.py:126-134: `y = y + self.fuse_layers[i][j](x[j])`, then `self.activ(y)`) with the
+ * `nn.Upsample(scale_factor=2 ** (j - i), mode="nearest")` of every UpSamplingBlock (hrnet.py:40-47) folded into the read:
+ *   y[n, h, w, c] = act( sum_{t = 0 .. nsrc-1} src[t][n, h >> shift[t], w >> shift[t], c] )
+ * y is dense NHWC [N,H,W,C] with C the PHYSICAL channel pitch (a multiple of 8; the sources' pad channels are zero, so y's are);
+ * src[t] is dense NHWC [N, H >> shift[t], W >> shift[t], C] - shift 0: an identity term or the output of a stride-2 chain, shift s > 0:
+ * the 1x1 convolution of an UpSamplingBlock, run at the coarse resolution. The sum is fp32 in the order t = 0, 1, ... (the
+ * reference's j = 0 .. B-1), rounded once (to nearest even) to the storage type; fp16 results are range-guarded. `src` and `shift` are
+ * HOST arrays, read before the launch (the pointers travel in the kernel arguments); only the tensors are borrowed afterwards.
+ * Limits: 1 <= nsrc <= 4, 0 <= shift[t] <= 3, act PCV_ACT_NONE or PCV_ACT_RELU. Refused with PCV_ERR_INVALID and a text before any
+ * device call: values outside those limits, C % 8 != 0, an empty output, H or W that is no multiple of 1 << shift[t], an unknown
+ * dtype, a NULL or not 16-byte aligned pointer, y equal to a source pointer; PCV_ERR_TOO_LARGE when y exceeds the 2 GiB window.
+ *   pcv_hr_fuse_supported   host arithmetic only, no context, no pointers: 1 when pcv_hr_fuse takes the shape, else 0 with the
+ *                           reason in pcv_last_error(NULL)
+ *   pcv_hr_fuse             the launch: no allocation, no synchronisation (capturable). */
+int pcv_hr_fuse_supported(int nsrc, const int* shift, int N, int H, int W, int C, int act, int dtype);
+int pcv_hr_fuse(pcv_ctx* ctx, const void* const* src, const int* shift, int nsrc, void* y, int N, int H, int W, int C, int act,
+                int dtype, void* stream);
 /* nn.AvgPool2d(k, stride=s), no padding (resnet.py:316-318, mobilenetv2.py:134-136); k == H == W is the
  * global-average-pool of the classifier tail. fp32 accumulation. */
 int pcv_avgpool2d(pcv_ctx* ctx, const void* x, void* y, int N, int H, int W, int C, int k, int s,

@@ -47,6 +47,7 @@ GHOST_INSTANCES(GHOST_DECLARE, PCV_F16)
 #include "aux_kernels.hpp"
 #include "cbam_kernels.hpp"
 #include "instnorm.hpp"
+#include "hrfuse.hpp"
 #include "resize_kernel.hpp"
 #include "classify_kernel.hpp"
 #include "head_gemm.hpp"
@@ -2481,6 +2482,70 @@ int pcv_interpolate(pcv_ctx* ctx, const void* x, void* y, int N, int H, int W, i
     if (int rc = flat_grid(ctx, "pcv_interpolate", (long long)N * Ho * Wo * (C / 8), &grid)) return rc;
     hipStream_t st = (hipStream_t)stream;
     for_dtype(dtype, [&](auto T) { interpolate_kernel<DT_OF(T)><<<grid, 256, 0, st>>>(x, y, N, H, W, C, Ho, Wo, bilinear, align_corners); });
+    return launched(ctx);
+}
+
+// ---- HRNet's multi-resolution fuse (hrnet.py:40-47,126-134; hrfuse.hpp) --------------------------------------------------------------
+// every check that needs no pointer and no context: PCV_OK, or the code with the reason in *why
+static int check_hr_fuse(int nsrc, const int* shift, int N, int H, int W, int C, int act, int dtype, const char** why) {
+    *why = nullptr;
+    if (nsrc < 1 || nsrc > kHrMaxSrc) *why = "needs 1 .. 4 sources";
+    else if (!shift) *why = "NULL shift array";
+    else if (!dtype_ok(dtype)) *why = "unknown dtype";
+    else if (act != PCV_ACT_NONE && act != PCV_ACT_RELU) *why = "the activation must be PCV_ACT_NONE or PCV_ACT_RELU";
+    else if (N <= 0 || H <= 0 || W <= 0 || C <= 0) *why = "empty output";
+    else if (C % 8 != 0) *why = "C (the physical channel pitch) must be a multiple of 8";
+    if (*why) return PCV_ERR_INVALID;
+    for (int t = 0; t < nsrc; ++t) {
+        if (shift[t] < 0 || shift[t] > kHrMaxShift) { *why = "a shift must be in 0 .. 3"; return PCV_ERR_INVALID; }
+        const int m = (1 << shift[t]) - 1;
+        if ((H & m) != 0 || (W & m) != 0) { *why = "H and W must be exact multiples of 1 << shift (the size does not divide)"; return PCV_ERR_INVALID; }
+    }
+    // (factor by factor: the product of four ints does not fit 64 bits)
+    unsigned long long ybytes = (unsigned long long)N * (unsigned long long)H;
+    if (in_window(ybytes)) ybytes *= (unsigned long long)W;
+    if (in_window(ybytes)) ybytes *= (unsigned long long)C * esize(dtype);
+    if (!in_window(ybytes)) { *why = kTensorTooLarge; return PCV_ERR_TOO_LARGE; }
+    return PCV_OK;
+}
+
+int pcv_hr_fuse_supported(int nsrc, const int* shift, int N, int H, int W, int C, int act, int dtype) {
+    const char* why = nullptr;
+    if (check_hr_fuse(nsrc, shift, N, H, W, C, act, dtype, &why) != PCV_OK) {
+        fail(nullptr, PCV_ERR_INVALID, std::string("pcv_hr_fuse_supported: ") + why);
+        return 0;
+    }
+    return 1;
+}
+
+int pcv_hr_fuse(pcv_ctx* ctx, const void* const* src, const int* shift, int nsrc, void* y, int N, int H, int W, int C, int act,
+                int dtype, void* stream) {
+    PCV_ENTER(ctx);
+    const char* why = nullptr;
+    if (int rc = check_hr_fuse(nsrc, shift, N, H, W, C, act, dtype, &why)) return fail(ctx, rc, std::string("pcv_hr_fuse: ") + why);
+    if (!src || !y) return fail(ctx, PCV_ERR_INVALID, "pcv_hr_fuse: NULL argument");
+    HrFuseParams p = {};
+    for (int t = 0; t < nsrc; ++t) {
+        if (!src[t]) return fail(ctx, PCV_ERR_INVALID, "pcv_hr_fuse: NULL source pointer");
+        if (src[t] == y) return fail(ctx, PCV_ERR_INVALID, "pcv_hr_fuse: y must not be one of the sources (not an in-place operation)");
+        if (!aligned16(src[t])) return fail(ctx, PCV_ERR_INVALID, "pcv_hr_fuse: pointers must be 16-byte aligned");
+        p.src[t] = src[t];
+        p.shift[t] = shift[t];
+    }
+    if (!aligned16(y)) return fail(ctx, PCV_ERR_INVALID, "pcv_hr_fuse: pointers must be 16-byte aligned");
+    p.y = y;
+    p.H = H; p.W = W; p.C8 = C / 8;
+    p.dC8 = make_fastdiv((uint32_t)p.C8);
+    p.dW = make_fastdiv((uint32_t)W);
+    p.dH = make_fastdiv((uint32_t)H);
+    const long long total = (long long)N * H * W * p.C8;             // one thread per 8-channel chunk; < 2^27: y fits the 2 GiB window
+    p.total = (uint32_t)total;
+    p.act = act;
+    p.ovf = ctx->ovf;
+    unsigned grid = 0;
+    if (int rc = stream_grid(ctx, "pcv_hr_fuse", total, &grid)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    for_dtype(dtype, [&](auto T) { launch_hr_fuse<DT_OF(T)>(nsrc, grid, st, p); });
     return launched(ctx);
 }
 

@@ -6,7 +6,7 @@
 
 __all__ = ['NHWC', 'DTYPES', 'default_dtype', 'set_compute_dtype', 'compute_dtype_of', 'Fp16Guard', 'fp16_overflow_count', 'from_nchw', 'to_nchw', 'ConvRunner',
            'MixConvRunner', 'ghost_dw', 'BnActRunner', 'IBNConvRunner', 'InstNormRunner', 'maxpool2d', 'avgpool2d', 'avgpool2d_pad', 'global_avgpool', 'se_excite', 'se_scale', 'se_forward', 'splat_forward', 'cbam_channel_gate', 'cbam_spatial', 'cbam_forward', 'channel_slice', 'cat_shuffle2', 'act_code',
-           'boundary', 'round8', 'channel_concat_into', 'interpolate', 'add', 'classify']
+           'boundary', 'round8', 'channel_concat_into', 'interpolate', 'add', 'hr_fuse', 'hr_fuse_supported', 'classify']
 
 import os
 import ctypes
@@ -793,6 +793,42 @@ def add(a: NHWC, b: NHWC, post_act: int = 0) -> NHWC:
     if a.t.shape != b.t.shape or a.dtype != b.dtype or not a.dense:
         raise RuntimeError("add: operands do not match")
     return se_scale(a, torch.ones((a.N, a.cpitch), dtype=torch.float32, device=a.device), b, post_act)
+
+
+def hr_fuse_supported(shifts, N: int, H: int, W: int, cpitch: int, act: int, dtype) -> bool:
+    """Whether `hr_fuse` takes this shape (pcv_hr_fuse_supported: host arithmetic, no context); the reason for a refusal is
+    the library's pcv_last_error(None)."""
+    sh = (ctypes.c_int * len(shifts))(*[int(s) for s in shifts])
+    return bool(_lib.lib().pcv_hr_fuse_supported(len(shifts), sh, N, H, W, cpitch, act, _CODE_OF_TORCH[dtype]))
+
+
+def hr_fuse(sources, shifts, act: int = 0) -> NHWC:
+    """HRNet's exchange for one output branch as ONE launch (pcv_hr_fuse; reference hrnet.py:40-47,126-134):
+    y[n, h, w] = act(sum_t sources[t][n, h >> shifts[t], w >> shifts[t]]), fp32 sum in list order, rounded once. A source with shift
+    s is the dense handle of the map H >> s x W >> s (an UpSamplingBlock's 1x1 output, never upsampled); the output size is that of
+    the shift-0 sources, or source 0 scaled up when there is none. Handles that do not fit together and shapes the kernel refuses
+    raise RuntimeError."""
+    sources, shifts = list(sources), [int(s) for s in shifts]
+    if not sources or len(sources) != len(shifts) or not all(isinstance(s, NHWC) for s in sources):
+        raise RuntimeError("hr_fuse: expected as many NHWC handles as shifts, got {} / {}".format(len(sources), len(shifts)))
+    if any(s < 0 or s > 8 for s in shifts):
+        raise RuntimeError("hr_fuse: shifts out of range: {}".format(shifts))
+    a = sources[0]
+    N, C, H, W = a.N, a.C, a.H << shifts[0], a.W << shifts[0]
+    for s, k in zip(sources, shifts):
+        if not s.dense or s.dtype != a.dtype or s.device != a.device or (s.N, s.C) != (N, C) or \
+                (s.H << k, s.W << k) != (H, W) or tuple(s.t.shape) != (N, s.H, s.W, s.cpitch):
+            raise RuntimeError("hr_fuse: source [{}, {}, {}, {}] (pitch {} / row pitch {}, {}) at shift {} does not fit the output "
+                               "[{}, {}, {}, {}] ({})".format(s.N, s.H, s.W, s.C, s.cpitch, s.wpitch, s.dtype, k, N, H, W, C, a.dtype))
+    y = torch.empty((N, H, W, a.cpitch), dtype=a.dtype, device=a.device)
+    src = (ctypes.c_void_p * len(sources))(*[s.t.data_ptr() for s in sources])
+    sh = (ctypes.c_int * len(shifts))(*shifts)
+    try:
+        _call(a.device, "hr_fuse", src, sh, len(sources), _ptr(y), N, H, W, a.cpitch, int(act), _CODE_OF_TORCH[a.dtype])
+    except _lib.PcvError as e:
+        raise RuntimeError("hr_fuse: the kernel refuses {} source(s) with shifts {} on [{}, {}, {}, {}]: {}".format(
+            len(sources), shifts, N, H, W, C, e))
+    return NHWC(y, N, H, W, C, cpitch=a.cpitch)
 
 
 def cat_shuffle2(a: NHWC, b: NHWC, half: int) -> NHWC:

@@ -38,7 +38,7 @@ extern "C" {
  *    likewise + pcv_classify_f32, + pcv_cbam_pool / _excite / _spatial_pool / _apply,
  *    + pcv_mixconv_packed_bytes / pcv_mixconv_pack / pcv_mixconv2d_fused, + pcv_bottleneck_supported / pcv_bottleneck_fused,
  *    + pcv_instnorm_workspace_bytes / pcv_instnorm_act, + pcv_ghost_supported / pcv_ghost_dw_fused and the activation code
- *    PCV_ACT_CLAMP01, + pcv_hr_fuse_supported / pcv_hr_fuse) */
+ *    PCV_ACT_CLAMP01, + pcv_hr_fuse_supported / pcv_hr_fuse, + pcv_gconvx_supported) */
 #define PCV_ABI_VERSION 5
 
 typedef struct pcv_ctx pcv_ctx;
@@ -274,6 +274,17 @@ int pcv_mixconv2d_fused(pcv_ctx* ctx, const pcv_conv_desc* d, const int* kernels
 int pcv_ghost_supported(const pcv_conv_desc* d);
 int pcv_ghost_dw_fused(pcv_ctx* ctx, const pcv_conv_desc* d, const void* m, const void* packed, const float* scale,
                        const float* shift, const void* residual, void* y, void* stream);
+/* Grouped 3x3 convolutions at RegNet's group widths: conv2 of RegNetBottleneck (regnet.py:60-64, conv3x3_block(groups=mid_channels //
+ * group_width); call site pytorchcv_amd/models/regnet.py, RegNetUnit.run) goes through pcv_conv2d_fused like every convolution, and
+ * the library routes it to csrc/gconvx.hpp - 3x3, pads 1, dilation 1, Cin == Cout, 16-bit storage, stride 1 or stride 2 on an even
+ * map, at most 112 columns, 8 / 16 / 24 / 40 / 48 / 56 / 64 channels per group with ANY number (>= 2) of groups - wherever the ResNeXt
+ * kernels (Cin % 64 == 0 with 4 / 8 / 16 / 32 channels per group) do not apply and the kernel measured faster than the generic one
+ * (the shape classes of DESIGN.md 5.1c‴: not at 64 per group, nor 40 ... 56 per group on a few wide-map classes). The blob of pcv_conv_pack carries that kernel's
+ * layout behind the generic one. A launch with a gate, a residual, a post_act, padded input pitches or a sliced y, and every other
+ * grouped shape, runs on the generic kernel as before; pcv_set_tuning(ctx, "gconvx", 0) (or "gconvr", 0) sends all of them there.
+ *   pcv_gconvx_supported  host arithmetic only: 1 when a plain pcv_conv2d_fused launch of `d` runs on that kernel, else 0 with the
+ *                         reason in pcv_last_error(NULL). */
+int pcv_gconvx_supported(const pcv_conv_desc* d);
 /* nn.MaxPool2d(k, s, p, ceil_mode) of ResInitBlock (resnet.py:255-258, floor) and ShuffleInitBlock (shufflenetv2.py:111-115,
  * ceil_mode=True): -inf padding; with ceil_mode the last window may hang over the bottom / right edge (PyTorch's rule). A NaN
  * in a window gives NaN, as in torch. y is [N, Ho, Wo, C] with PyTorch's output size; an empty one is PCV_ERR_INVALID. */

@@ -73,6 +73,7 @@ _SIGS = {
     "pcv_mixconv2d_fused": (_I, [_VP, ctypes.POINTER(ConvDesc), ctypes.POINTER(_I), _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "pcv_ghost_supported": (_I, [ctypes.POINTER(ConvDesc)]),
     "pcv_ghost_dw_fused": (_I, [_VP, ctypes.POINTER(ConvDesc), _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "pcv_gconvx_supported": (_I, [ctypes.POINTER(ConvDesc)]),
     "pcv_hr_fuse_supported": (_I, [_I, ctypes.POINTER(_I), _I, _I, _I, _I, _I, _I]),
     "pcv_hr_fuse": (_I, [_VP, ctypes.POINTER(_VP), ctypes.POINTER(_I), _I, _VP, _I, _I, _I, _I, _I, _I, _VP]),
     "pcv_maxpool2d": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _VP]),

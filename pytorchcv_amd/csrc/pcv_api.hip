@@ -24,6 +24,9 @@
 #include "bnu.hpp"
 #include "gconv3x3.hpp"
 #include "gconv3x3r.hpp"
+#include "gconvx.hpp"
+GCONVX_INSTANCES(GCONVX_DECLARE, PCV_BF16)
+GCONVX_INSTANCES(GCONVX_DECLARE, PCV_F16)
 #include "mbconv.hpp"
 #include "mbw_inst.hpp"
 #include "mbr_inst.hpp"
@@ -101,6 +104,7 @@ struct pcv_ctx {
     int use_mbr_xl = 1;         // mbr.hpp instantiations that stage x through LDS; 0: never (A/B)
     int use_mbw = 1;            // fused inverted-residual units with Cin <= 32 run the wave-private kernel (mbw.hpp; 8 / 16: force that pixel-block width); 0: mbconv.hpp
     int use_gconvr = 1;         // grouped 3x3 stride 2 / 32 channels per group on the row-tile kernel (gconv3x3r.hpp); 0 = generic implicit GEMM
+    int use_gconvx = 1;         // grouped 3x3 at the group widths gconv3x3(r).hpp do not take (8..64 channels per group, any channel count) on gconvx.hpp; 0 (or "gconvr" 0) = generic implicit GEMM
     int use_d1x1 = -1;          // K-heavy 1x1 layers on d3q_kernel's 1x1 mode: -1 = pick_d1x1, 0 = never, n > 0 = force shape n - 1 where eligible
     int use_head = 1;           // fp32 dense layers on 1x1 maps run head_gemm.hpp (0: the generic implicit-GEMM tiles)
     int use_stem32 = 1;         // stems with <= 32 output channels run the 32-row form of the stem kernel (0: the 64-row form; A/B, tests)
@@ -127,6 +131,7 @@ struct pcv_ctx {
     // < 80 SGPRs, where the query is exact (MI355X_MICROARCH.md). Where one slot serves both 16-bit types it holds the fp16 instance's figure.
     int igemm_bpc[3][2][TILE_COUNT][3] = {};     // [dt][variant: 0 regular, 1 ragged/f32-out][tile][khw slot]
     int gconv_bpc[3] = {2, 2, 2};                // [gconv_slot(W)]
+    int gconvx_bpc[2] = {2, 2};                  // [tile of 4 / 7 pixel blocks]: the widest group's (64 channels, stride 1), used by every width
     int stem_bpc[2] = {1, 1};                    // [bf16, fp16]: the plain 64-row form's, used by every form
     int pair_bpc[2] = {1, 1};                    // [PB == 4, PB == 2]; the gated form launches with [1]
     int pair_idc_bpc = 1;
@@ -265,6 +270,8 @@ struct ConvPlan {
     bool d3i = false;         // dense 3x3/s1/p1, 16 bit, 256 / 512 input channels, Cout % 64 == 0: a fragment-ordered copy of the weights for d3i_conv.hpp
     bool d1i = false;         // 1x1/s1, 16 bit, 1024 / 2048 input channels, Cout % 64 == 0: the same fragment-ordered copy for d1i_conv.hpp
     size_t d3i_off = 0;       // follows the generic blob (whether a launch takes that kernel depends on the map size)
+    bool gconvx = false;      // grouped 3x3/p1, stride 1 or 2, Cin == Cout, 8/16/24/40/48/56/64 channels per group and not `gconv`: a blob for gconvx.hpp
+    size_t gconvx_off = 0;    // behind the generic one (the launch may still fall back: pitches, a residual, an odd map at stride 2)
     size_t gconv_off = 0;     // one (the choice between the two kernels depends on the map width, known only at launch)
     std::vector<uint32_t> ktab;   // built only when tables == true
     std::vector<uint32_t> ksrc;
@@ -273,6 +280,14 @@ struct ConvPlan {
 // A descriptor built by a binding that mirrors another layout of pcv_conv_desc (a stale ctypes stub) is refused, not read.
 static const char* const kStaleDesc = "pcv_conv_desc.struct_size does not match this library (stale binding: compare pcv_conv_desc_size() / PCV_ABI_VERSION)";
 static inline bool desc_stale(const pcv_conv_desc& d) { return d.struct_size != (int32_t)sizeof(pcv_conv_desc); }
+
+// gconvx.hpp's group widths (GCONVX_WIDTHS): index into the kernel table, -1 = not one of them
+static inline int gconvx_width(int cg) {
+    static const int kWidths[7] = {8, 16, 24, 40, 48, 56, 64};
+    for (int i = 0; i < 7; ++i)
+        if (kWidths[i] == cg) return i;
+    return -1;
+}
 
 static const char* plan_conv(const pcv_conv_desc& d, ConvPlan& P, bool tables) {
     if (desc_stale(d)) return kStaleDesc;
@@ -362,6 +377,13 @@ static const char* plan_conv(const pcv_conv_desc& d, ConvPlan& P, bool tables) {
         P.gconv_kt = P.Cg_in == 32 ? 9 : 5;
         P.gconv_off = (P.total_bytes + 15) / 16 * 16;
         P.total_bytes = P.gconv_off + (size_t)(d.Cin / 16) * P.gconv_kt * 16 * 32 * P.ES;
+    }
+    P.gconvx = !P.gconv && d.groups > 1 && d.kh == 3 && d.kw == 3 && d.stride_h == d.stride_w && (d.stride_h == 1 || d.stride_h == 2) &&
+               d.dil_h == 1 && d.dil_w == 1 && d.pad_t == 1 && d.pad_l == 1 && d.pad_b == 1 && d.pad_r == 1 && d.Cin == d.Cout && P.ES == 2 &&
+               gconvx_width(P.Cg_in) >= 0 && d.out_dtype == d.dtype;
+    if (P.gconvx) {
+        P.gconvx_off = (P.total_bytes + 15) / 16 * 16;
+        P.total_bytes = P.gconvx_off + (size_t)gconvx_packed_elems(d.groups, P.Cg_in) * P.ES;
     }
     P.d3i = P.conv3 && P.ES == 2 && (d.Cin == 256 || d.Cin == 512) && d.Cout % D3ICfg::CW == 0 && d.out_dtype == d.dtype &&
             P.wrows >= d.Cout && P.Kpad == 9 * d.Cin;
@@ -526,6 +548,43 @@ static bool plan_gconvr(int stride, int H, int W, int Ho, int Wo, GConvRPlan& g)
             g.R = R; g.XH = XH; g.xl = rows / 32; g.win = win;
             return true;
         }
+    }
+    return false;
+}
+// ---- any-width grouped kernel (gconvx.hpp): [bf16, fp16][stride - 1][pixel blocks 4, 7][gconvx_width] ---------------------------
+#define GCONVX_KROW(DT, S, PB)                                                                                               \
+    {kernel_of(gconvx_kernel<DT, S, 8, PB>, 256, kGConvXMaxLds), kernel_of(gconvx_kernel<DT, S, 16, PB>, 256, kGConvXMaxLds),  \
+     kernel_of(gconvx_kernel<DT, S, 24, PB>, 256, kGConvXMaxLds), kernel_of(gconvx_kernel<DT, S, 40, PB>, 256, kGConvXMaxLds), \
+     kernel_of(gconvx_kernel<DT, S, 48, PB>, 256, kGConvXMaxLds), kernel_of(gconvx_kernel<DT, S, 56, PB>, 256, kGConvXMaxLds), \
+     kernel_of(gconvx_kernel<DT, S, 64, PB>, 256, kGConvXMaxLds)}
+#define GCONVX_KTYPE(DT) {{GCONVX_KROW(DT, 1, 4), GCONVX_KROW(DT, 1, 7)}, {GCONVX_KROW(DT, 2, 4), GCONVX_KROW(DT, 2, 7)}}
+static const Kernel kGConvX[2][2][2][7] = {GCONVX_KTYPE(PCV_BF16), GCONVX_KTYPE(PCV_F16)};
+// The tile of a launch: R whole output rows (R Wo <= 112 pixels: the 4- or the 7-block instantiation) x GB whole groups.
+//   * R: the largest (R + 2) / R (stride 2: (2 R + 1) / 2 R) of the window's rows are halo, so as many rows as the pixel cap and LDS
+//     allow - but not at the price of fewer than four (group, slab) units, one per wave;
+//   * GB: up to 128 channels (more units only lengthen a block's serial run), as many as the window leaves room for, then evened
+//     out over the channel blocks (19 groups at 16 per block: 10 + 9, not 16 + 3).
+// Everything here follows from the descriptor alone (pcv_gconvx_supported).
+struct GConvXPlan { int R, GB, pbi, win, pitch, lds; };
+static bool plan_gconvx(int stride, int H, int W, int Ho, int Wo, int groups, int Cg, GConvXPlan& g) {
+    if (stride == 2 && ((H | W) & 1)) return false;                // the flat-row identity needs H = 2 Ho; even W keeps column 2 wo + 1 inside
+    if (W > 112 || Ho <= 0 || Wo <= 0) return false;
+    const int cpg = Cg / 8, sl = (Cg + 15) / 16;
+    const int min_gb = std::min(groups, (4 + sl - 1) / sl);        // four units
+    const int want_gb = std::min(groups, std::max(min_gb, 128 / Cg));
+    for (int R = 16 * kGConvXPB[1] / Wo; R >= 1; --R) {
+        const int win = stride == 2 ? (2 * R + 1) * W + 2 : (R + 2) * W + 2;
+        int p16 = kGConvXMaxLds / (16 * win);                      // 16-byte chunks per window pixel that fit ...
+        if (p16 % 2 == 0) --p16;                                   // ... as an odd pitch
+        const int fit_gb = p16 / cpg;
+        if (fit_gb < (R == 1 ? 1 : min_gb)) continue;
+        int gb = std::min(want_gb, fit_gb);
+        const int ncb = (groups + gb - 1) / gb;
+        gb = (groups + ncb - 1) / ncb;
+        g.R = R; g.GB = gb; g.pbi = R * Wo <= 16 * kGConvXPB[0] ? 0 : 1; g.win = win;
+        g.pitch = 16 * ((gb * cpg) | 1);
+        g.lds = win * g.pitch;
+        return true;
     }
     return false;
 }
@@ -813,6 +872,10 @@ static int enable_kernels(pcv_ctx* ctx) {
         for (int s = 1; s <= 2; ++s)
             for (int kt = 5; kt <= 9; kt += 4) on(gconvr_kernel(dt, s, kt));
     for (int t = 0; t < 2; ++t)
+        for (int s = 0; s < 2; ++s)
+            for (int pbi = 0; pbi < 2; ++pbi)
+                for (int wi = 0; wi < 7; ++wi) on(kGConvX[t][s][pbi][wi], (t == 1 && s == 0 && wi == 6) ? &ctx->gconvx_bpc[pbi] : nullptr);
+    for (int t = 0; t < 2; ++t)
         for (int nchw = 0; nchw < 2; ++nchw)
             for (int form = 0; form < 3; ++form) on(kStem[t][nchw][form], (nchw == 0 && form == STEM_PLAIN) ? &ctx->stem_bpc[t] : nullptr);
     for (int form = 0; form < 4; ++form) {
@@ -965,7 +1028,7 @@ static const struct { const char* key; int pcv_ctx::*field; } kTuningKeys[] = {
     {"head", &pcv_ctx::use_head},        {"stem32", &pcv_ctx::use_stem32},         {"d1x1", &pcv_ctx::use_d1x1},
     {"gconvr", &pcv_ctx::use_gconvr},    {"mbw", &pcv_ctx::use_mbw},               {"mbr", &pcv_ctx::use_mbr},
     {"mbr_xl", &pcv_ctx::use_mbr_xl},    {"dw_th", &pcv_ctx::dw_th},               {"dw_flags", &pcv_ctx::dw_flags},
-    {"wstat", &pcv_ctx::use_wstat},      {"bnu_band", &pcv_ctx::bnu_band},
+    {"wstat", &pcv_ctx::use_wstat},      {"bnu_band", &pcv_ctx::bnu_band},         {"gconvx", &pcv_ctx::use_gconvx},
 };
 int pcv_set_tuning(pcv_ctx* ctx, const char* key, int value) {
     if (!ctx || !key) return PCV_ERR_INVALID;
@@ -1147,6 +1210,8 @@ int pcv_conv_pack(pcv_ctx* ctx, const pcv_conv_desc* d, const float* w, void* pa
     unsigned grid = 0, ggrid = 0;
     if (int rc = flat_grid(ctx, "pcv_conv_pack", (long long)P.ngb * P.wrows * P.Kpad, &grid)) return rc;
     if (int rc = flat_grid(ctx, "pcv_conv_pack", P.gconv ? (long long)(d->Cin / 16) * P.gconv_kt * 16 * 32 : 0, &ggrid)) return rc;
+    if (P.gconvx)
+        if (int rc = flat_grid(ctx, "pcv_conv_pack", gconvx_packed_elems(d->groups, P.Cg_in), &ggrid)) return rc;
     // load-time only: synchronous uploads of the two small host-built tables
     uint32_t* ksrc_dev = nullptr;
     HIP_TRY(ctx, hipStreamSynchronize(s));
@@ -1176,6 +1241,10 @@ int pcv_conv_pack(pcv_ctx* ctx, const pcv_conv_desc* d, const float* w, void* pa
             if (P.gconv_kt == 9) pack_gconv32_kernel<DT_OF(T)><<<ggrid, 256, 0, s>>>(w, gout, d->Cin);
             else pack_gconv_kernel<DT_OF(T)><<<ggrid, 256, 0, s>>>(w, gout, d->Cin, P.Cg_in);
         });
+    }
+    if (P.gconvx) {
+        void* gout = static_cast<char*>(packed) + P.gconvx_off;
+        for_dtype16(d->dtype, [&](auto T) { pack_gconvx_kernel<DT_OF(T)><<<ggrid, 256, 0, s>>>(w, gout, d->groups, P.Cg_in); });
     }
     if (P.d3i || P.d1i) {
         const int total = (int)((P.total_bytes - P.d3i_off) / 16);
@@ -1255,6 +1324,7 @@ enum ConvKernel {
     CK_STEM,        // stem_conv.hpp: Cin <= 4, stride 2 (+ fused max-pool, + fp32 NCHW input)
     CK_GCONV_ROWS,  // gconv3x3r.hpp: grouped 3x3, stride 2 or 32 channels per group
     CK_GCONV_FLAT,  // gconv3x3.hpp: grouped 3x3, stride 1, 4 / 8 / 16 channels per group
+    CK_GCONVX,      // gconvx.hpp: grouped 3x3 at the widths and channel counts the two above do not take (RegNet)
     CK_D3I,         // d3i_conv.hpp: dense 3x3 / s1 / p1, 16 bit, 256 input channels on maps up to 14 x 14 or 512 up to 7 x 7 (image(s) in LDS, weights straight to registers)
     CK_D1I,         // d1i_conv.hpp: 1x1 / s1, 16 bit, 1024 / 2048 input channels (activations streamed through LDS, weights straight to registers)
     CK_D3K,         // d3k_conv.hpp: dense 3x3 / s1 / p1, 16 bit, 128 input channels on 28-wide maps (weights in registers / AGPRs)
@@ -1270,6 +1340,7 @@ struct ConvRoute {
     ConvKernel kernel = CK_IGEMM;
     int shape = -1;             // CK_D3Q / CK_D3Q_1X1: index into kD3 / kD1
     GConvRPlan rows{};          // CK_GCONV_ROWS
+    GConvXPlan xrows{};         // CK_GCONVX
     int tile = TILE_C128, khw = 0;      // CK_IGEMM: tile configuration, tap mode (0 table, 1 = 1x1, 9 = 3x3)
     bool special = false;       // CK_IGEMM: ragged channel count or fp32 output (the descriptor-driven 128 x 128 variants)
 };
@@ -1324,6 +1395,43 @@ static void route_igemm(const pcv_ctx* ctx, const pcv_conv_desc* d, const ConvPl
     R.khw = khw;
 }
 
+// The shape classes (channels per group, stride, map width) on which gconvx.hpp measured FASTER than the generic kernel at batch 256
+// (five interleaved runs against the commit before it, slowest against fastest: profiles/experiments/gconvx_kernel.md). Measured at
+// 8, 24, 48 and 56 channels per group, then at 16, 40 and 64 with 16 following 8 / 24 and 40 following 48 (both confirmed). Lost and
+// sent back to the generic kernel: 48 (and 40) per group at stride 2 on 28 .. 56-wide maps (six units on four waves), 56 per group at
+// stride 2 on maps wider than 56 and at stride 1 on maps wider than 28 (the three-group layers of regnety080's first stage), and 64
+// per group everywhere (regnety040: slower on five of its six layers, 3 % faster on one) - its instantiation stays for the next attempt.
+static bool gconvx_pays(int cg, int stride, int W) {
+    if (cg <= 24) return true;
+    if (cg <= 48) return !(stride == 2 && W >= 28 && W <= 56);
+    if (cg > 56) return false;
+    return !((stride == 2 && W > 56) || (stride == 1 && W > 28));
+}
+
+// Why a plain launch of `d` does not run on gconvx.hpp (nullptr: it does; *out then holds its tile). gconv_ok's launch conditions:
+// no gate, no residual, no post_act, dense pitches, no sliced output, tensors below 2 GiB.
+static const char* gconvx_launch_why(const pcv_conv_desc& d, const ConvPlan& P, const ConvGeom& G, bool gated, GConvXPlan* out) {
+    if (!P.gconvx) {
+        if (P.gconv) return "the shape belongs to the ResNeXt kernels (C % 64 == 0, 4 / 8 / 16 / 32 channels per group: gconv3x3.hpp, gconv3x3r.hpp)";
+        if (P.ES != 2 || d.out_dtype != d.dtype) return "16-bit storage only, out_dtype == dtype";
+        if (d.groups <= 1 || d.kh != 3 || d.kw != 3 || d.Cin != d.Cout) return "needs a grouped 3x3 convolution with Cin == Cout";
+        if (d.dil_h != 1 || d.dil_w != 1 || d.pad_t != 1 || d.pad_l != 1 || d.pad_b != 1 || d.pad_r != 1) return "needs padding 1 and dilation 1";
+        if (d.stride_h != d.stride_w || (d.stride_h != 1 && d.stride_h != 2)) return "stride 1 or 2 only";
+        return "channels per group must be 8, 16, 24, 40, 48, 56 or 64";
+    }
+    if (gated) return "a gated launch runs on the generic kernel";
+    if (d.has_residual || d.post_act != PCV_ACT_NONE) return "a residual / post_act launch runs on the generic kernel";
+    if (G.sliced_y) return "a sliced output (y_cpitch) runs on the generic kernel";
+    if (G.cpitch != d.Cin || G.wpitch != d.W) return "padded input pitches run on the generic kernel";
+    if (G.M64 * (unsigned long long)d.Cin * 2ull >= 0x80000000ull || !in_window(G.xbytes)) return kTensorTooLarge;
+    GConvXPlan g;
+    if (!plan_gconvx(d.stride_h, d.H, d.W, P.Ho, P.Wo, d.groups, P.Cg_in, g))
+        return "the map is odd at stride 2 or wider than 112 columns";
+    if (!gconvx_pays(P.Cg_in, d.stride_h, d.W)) return "measured slower than the generic kernel on this shape class (channels per group, stride, map width)";
+    if (out) *out = g;
+    return nullptr;
+}
+
 static ConvRoute route_conv(const pcv_ctx* ctx, const pcv_conv_desc* d, const ConvPlan& P, const ConvGeom& G, const ConvArgs& A) {
     ConvRoute R;
     if (P.stem) { R.kernel = CK_STEM; return R; }
@@ -1333,6 +1441,12 @@ static ConvRoute route_conv(const pcv_ctx* ctx, const pcv_conv_desc* d, const Co
     if (gconv_ok && ctx->use_gconvr != 0 && (d->stride_h == 2 || P.gconv_kt == 9) &&
         plan_gconvr(d->stride_h, d->H, d->W, P.Ho, P.Wo, R.rows)) { R.kernel = CK_GCONV_ROWS; return R; }
     if (gconv_ok && d->stride_h == 1 && P.gconv_kt == 5 && d->W <= 63) { R.kernel = CK_GCONV_FLAT; return R; }
+    // the group widths and channel counts the two kernels above were not built for (P.gconv false), under the same launch conditions;
+    // "gconvr" 0 switches this kernel off too (tests pin the generic kernel with it)
+    if (ctx->use_gconvx != 0 && ctx->use_gconvr != 0 && gconvx_launch_why(*d, P, G, A.gate != nullptr, &R.xrows) == nullptr) {
+        R.kernel = CK_GCONVX;
+        return R;
+    }
     const bool clamp_acts = d->act <= PCV_ACT_RELU6 && d->post_act <= PCV_ACT_RELU6;       // the 8-wave kernel's branch-free epilogue
     if (P.conv3 && !A.gate && ctx->use_d3x3 != 0 && d->dtype != PCV_F32 && clamp_acts && A.scale && A.shift &&
         G.M64 * (unsigned long long)d->Cout * 2ull < 0x80000000ull &&
@@ -1460,6 +1574,35 @@ static int launch_gconv_rows(pcv_ctx* ctx, const pcv_conv_desc* d, const ConvPla
     if (nb > nT) nb = nT;
     nb = (nb + 7) / 8 * 8;
     return launch(ctx, gconvr_kernel(d->dtype, d->stride_h, P.gconv_kt, lds), (unsigned)nb, A.stream, q);
+}
+
+static int launch_gconvx(pcv_ctx* ctx, const pcv_conv_desc* d, const ConvPlan& P, const ConvGeom& G, const ConvArgs& A,
+                         const GConvXPlan& gx) {
+    GConvXParams q;
+    std::memset(&q, 0, sizeof(q));
+    q.x = A.x; q.y = A.y; q.scale = A.scale; q.shift = A.shift; q.ovf = ctx->ovf;
+    q.w = static_cast<const char*>(A.packed) + P.gconvx_off;
+    q.x_bytes = (uint32_t)G.xbytes; q.w_bytes = (uint32_t)(P.total_bytes - P.gconvx_off);
+    q.y_bytes = (uint32_t)(G.M64 * (unsigned long long)d->Cin * 2ull);
+    q.Min = d->N * d->H * d->W; q.Mout = (int)G.M64;
+    q.W = d->W; q.Wo = P.Wo; q.Ho = P.Ho; q.C = d->Cin;
+    q.G = d->groups; q.GB = gx.GB;
+    q.R = gx.R; q.RWo = gx.R * P.Wo; q.npb = (q.RWo + 15) / 16; q.win = gx.win; q.pitch = gx.pitch;
+    q.div_wo = make_fastdiv((uint32_t)P.Wo);
+    q.div_ho = make_fastdiv((uint32_t)P.Ho);
+    q.div_cpb = make_fastdiv((uint32_t)(gx.GB * (P.Cg_in / 8)));
+    const long long rows = (long long)d->N * P.Ho;
+    q.nRowTiles = (int)((rows + gx.R - 1) / gx.R);
+    const long long nT = (long long)q.nRowTiles * ((d->groups + gx.GB - 1) / gx.GB);
+    if (nT >= 0x7FFFFFFFll) return fail(ctx, PCV_ERR_TOO_LARGE, "pcv_conv2d_fused: too many tiles; split the batch");
+    q.nTiles = (int)nT;
+    q.act = d->act;
+    long long nb = block_slots(ctx, ctx->gconvx_bpc[gx.pbi]);
+    if (nb > nT) nb = nT;
+    nb = (nb + 7) / 8 * 8;
+    Kernel k = kGConvX[d->dtype == PCV_BF16 ? 0 : 1][d->stride_h - 1][gx.pbi][gconvx_width(P.Cg_in)];
+    k.lds = gx.lds;
+    return launch(ctx, k, (unsigned)nb, A.stream, q);
 }
 
 static int launch_gconv_flat(pcv_ctx* ctx, const pcv_conv_desc* d, const ConvPlan& P, const ConvGeom& G, const ConvArgs& A) {
@@ -1707,6 +1850,7 @@ static int conv2d_impl(pcv_ctx* ctx, const pcv_conv_desc* d, const void* x, cons
         case CK_STEM: return launch_stem(ctx, d, P, G, A);
         case CK_GCONV_ROWS: return launch_gconv_rows(ctx, d, P, G, A, R.rows);
         case CK_GCONV_FLAT: return launch_gconv_flat(ctx, d, P, G, A);
+        case CK_GCONVX: return launch_gconvx(ctx, d, P, G, A, R.xrows);
         case CK_D3I: case CK_D1I: case CK_D3K: case CK_D3C: case CK_D3W: case CK_D3Q: case CK_P1R: case CK_D3Q_1X1:
             return launch_d3(ctx, d, P, G, A, R);                      // the kernels that take D3Params
         case CK_HEAD: return launch_head(ctx, d, P, G, A);
@@ -1733,6 +1877,24 @@ int pcv_fc_f32(pcv_ctx* ctx, const float* in, const float* w, const float* b, fl
     if (!in || !w || !b || !out || N <= 0 || K <= 0 || J <= 0) return fail(ctx, PCV_ERR_INVALID, "pcv_fc_f32: bad argument");
     launch_se_fc(in, w, b, out, N, K, J, act, (hipStream_t)stream);
     return launched(ctx);
+}
+
+int pcv_gconvx_supported(const pcv_conv_desc* d) {
+    if (!d) { fail(nullptr, PCV_ERR_INVALID, "pcv_gconvx_supported: NULL argument"); return 0; }
+    ConvPlan P;
+    const char* why = plan_conv(*d, P, false);
+    if (!why && (d->N <= 0 || d->H <= 0 || d->W <= 0 || P.Ho <= 0 || P.Wo <= 0)) why = "empty input or output";
+    if (!why) {
+        ConvGeom G;
+        G.cpitch = d->x_cpitch > 0 ? d->x_cpitch : d->Cin;
+        G.wpitch = d->x_wpitch > 0 ? d->x_wpitch : d->W;
+        G.xbytes = (unsigned long long)d->N * d->H * G.wpitch * G.cpitch * P.ES;
+        G.M64 = (unsigned long long)d->N * P.Ho * P.Wo;
+        G.sliced_y = d->y_cpitch > 0 && d->y_cpitch != d->Cout;
+        why = gconvx_launch_why(*d, P, G, false, nullptr);
+    }
+    if (why) { fail(nullptr, PCV_ERR_INVALID, std::string("pcv_gconvx_supported: ") + why); return 0; }
+    return 1;
 }
 
 int pcv_conv2d_maxpool_supported(const pcv_conv_desc* d, int k, int s, int p, int ceil_mode) {

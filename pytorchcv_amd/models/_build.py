@@ -3,13 +3,21 @@
     constructor and a handful of options - the trunk / head / variant-factory code is written once here. The attribute names
     the builder emits (`features.init_block`, `features.stage{i}.unit{j}`, `features.final_block`, `features.final_pool`,
     `output`) are the reference's state_dict contract, not a choice.
+
+    A family is three things. (1) A net class on `ClassifierNet`: add `init_block` to `self.features`, call `add_stages` with a
+    stage table and a `make_unit(cin, cout, stride, i, j)` - per-unit tables (`exp_channels[i][j]`, `use_se[i][j]`, ...) are read
+    through `i, j` -, add `final_block` / `post_activ` where the reference has one, and end with `self.finish(width)`. (2) A
+    `get_<family>(..., model_name, pretrained, root, **kwargs)` that turns a depth / version / width scale into the stage table.
+    (3) `register_variants(__name__, get_<family>, {name: kwargs})` for the named factories. The residual families share their
+    unit base, stage container and depth table (resnet.py: `SkipUnit`, `ResStage`, `resnet_layers`).
 """
 
 __all__ = ['add_stages', 'ClassifierNet', 'register_variants', 'scale_widths', 'stage_table']
 
 import sys
 import torch.nn as nn
-from ._tail import AvgPool2dNHWC, LinearHead, run_net, maybe_load_pretrained, init_conv_params, DEFAULT_ROOT
+from ._tail import AvgPool2dNHWC, LinearHead, run_net, init_conv_params
+from .. import engine
 
 
 def stage_table(widths, depths):
@@ -37,19 +45,21 @@ def add_stages(features, in_channels, table, make_unit, container=nn.Sequential,
 
 
 class ClassifierNet(nn.Module):
-    """`features` (filled by the subclass through `self.trunk(...)`) + global 7x7 average pool + `output` classifier; forward =
-    NCHW fp32 in, hot path, fp32 logits out (`_tail.run_net`). Subclasses call `finish(width, head=...)` last."""
+    """`features` (filled by the subclass, usually through `add_stages`) + 7x7 average pool + `output` classifier; forward =
+    NCHW fp32 in, hot path, fp32 logits out (`_tail.run_net`). Subclasses call `finish(width, ...)` last: `head` replaces the
+    Linear classifier (a subclass whose head is not called as `output(a)` overrides `_head`), `pool` the 7x7 `final_pool`."""
     def __init__(self, in_size, num_classes):
         super(ClassifierNet, self).__init__()
         self.in_size = in_size
         self.num_classes = num_classes
         self.features = nn.Sequential()
 
-    def finish(self, width, head=None, init=init_conv_params):
-        self.features.add_module("final_pool", AvgPool2dNHWC(kernel_size=7, stride=1, fp32_out=True))
+    def finish(self, width, head=None, init=init_conv_params, pool=None):
+        self.features.add_module("final_pool", pool if pool is not None else AvgPool2dNHWC(kernel_size=7, stride=1, fp32_out=True))
         self.output = head if head is not None else LinearHead(in_features=width, out_features=self.num_classes)
         if init is not None:
             init(self)
+        engine.stamp_family_dtype(self)        # `pcv_16bit` of the net class: sub-modules called on their own resolve "auto" like the net
 
     def _head(self, a):
         return self.output(a)
@@ -71,13 +81,10 @@ def register_variants(module_name, getter, variants, key="model_name"):
             merged[key] = name
             return getter(**merged)
         factory.__name__ = factory.__qualname__ = name
+        factory.__module__ = module_name
         factory.__doc__ = "{}: {}".format(name, ", ".join("{}={!r}".format(k, v) for k, v in sorted(fixed.items())))
         return factory
     for name, fixed in variants.items():
         setattr(mod, name, make(name, fixed))
         if name not in mod.__all__:
             mod.__all__.append(name)
-
-
-def pretrained_or_not(net, model_name, pretrained, root):
-    return maybe_load_pretrained(net, model_name, pretrained, root)

@@ -3,7 +3,7 @@
     nn.AvgPool2d (same attribute names, no state), the classifier tail and the pretrained-weights hook of every factory.
 """
 
-__all__ = ['MaxPool2dNHWC', 'AvgPool2dNHWC', 'AvgPool2dPadNHWC', 'GlobalAvgPool2dNHWC', 'LinearHead', 'run_net', 'check_channels', 'maybe_load_pretrained', 'init_conv_params']
+__all__ = ['MaxPool2dNHWC', 'AvgPool2dNHWC', 'AvgPool2dPadNHWC', 'GlobalAvgPool2dNHWC', 'LinearHead', 'dropout_fc_head', 'run_net', 'check_channels', 'maybe_load_pretrained', 'init_conv_params']
 
 import os
 import torch
@@ -73,6 +73,16 @@ class LinearHead(nn.Linear):
             raise RuntimeError("classifier expects a 1x1 pooled map, got {}x{} (input size must match in_size)".format(x.H, x.W))
         y = self._pcv_runner.run(x, out_fp32=True)
         return y.t.view(y.N, -1)
+
+
+def dropout_fc_head(in_features, num_classes, dropout_rate):
+    """`output` = Sequential([dropout,] fc) (reference resnesta.py:262-267, efficientnet.py:341-347); the dropout is the identity
+    at inference and never launched, so the nets call `output.fc`."""
+    head = nn.Sequential()
+    if dropout_rate > 0.0:
+        head.add_module("dropout", nn.Dropout(p=dropout_rate))
+    head.add_module("fc", LinearHead(in_features=in_features, out_features=num_classes))
+    return head
 
 
 class _LinearAsConv(object):

@@ -11,10 +11,11 @@ __all__ = ['CbamResNet', 'cbam_resnet18', 'cbam_resnet34', 'cbam_resnet50', 'cba
 
 import torch
 import torch.nn as nn
-from .common.conv import conv1x1_block, conv7x7_block
+from .common.conv import conv7x7_block
 from .common.att import fold_bn_into_fc, _FoldedMlp
-from .resnet import ResInitBlock, ResBlock, ResBottleneck
-from ._tail import AvgPool2dNHWC, LinearHead, run_net, maybe_load_pretrained, init_conv_params, DEFAULT_ROOT
+from .resnet import SkipUnit, ResInitBlock, ResBlock, ResBottleneck, resnet_channels
+from ._build import ClassifierNet, add_stages, register_variants
+from ._tail import maybe_load_pretrained, DEFAULT_ROOT
 from .. import engine
 
 
@@ -105,80 +106,40 @@ class CbamBlock(nn.Module):
         return engine.boundary(self, x, lambda a: self._run(a, residual, post_act))
 
 
-class CbamResUnit(nn.Module):
+class CbamResUnit(SkipUnit):
     """relu(cbam(body(x)) + identity) (reference cbamresnet.py:131-183)."""
     def __init__(self, in_channels, out_channels, stride, bottleneck):
         super(CbamResUnit, self).__init__()
-        self.resize_identity = (in_channels != out_channels) or (stride != 1)
         if bottleneck:
             self.body = ResBottleneck(in_channels=in_channels, out_channels=out_channels, stride=stride, conv1_stride=False)
         else:
             self.body = ResBlock(in_channels=in_channels, out_channels=out_channels, stride=stride)
-        if self.resize_identity:
-            self.identity_conv = conv1x1_block(in_channels=in_channels, out_channels=out_channels, stride=stride, activation=None)
-        self.cbam = CbamBlock(channels=out_channels)
+        self.add_skip(in_channels, out_channels, stride, activation=None)
+        self.cbam = CbamBlock(channels=out_channels)          # the reference has it between the skip block and the activation
         self.activ = nn.ReLU(inplace=True)
 
     def _run(self, a):
-        identity = self.identity_conv(a) if self.resize_identity else a
+        identity = self._identity(a)
         return self.cbam(self.body(a), residual=identity, post_act=self.activ)      # the body without its own skip add
 
-    def forward(self, x):
-        return engine.boundary(self, x, self._run)
 
-
-class CbamResNet(nn.Module):
+class CbamResNet(ClassifierNet):
     """`features` (init_block, stage1..4 of unit1..n, final_pool) + `output` Linear (reference cbamresnet.py:186-253)."""
     def __init__(self, channels, init_block_channels, bottleneck, in_channels=3, in_size=(224, 224), num_classes=1000):
-        super(CbamResNet, self).__init__()
-        self.in_size = in_size
-        self.num_classes = num_classes
-        self.features = nn.Sequential()
+        super(CbamResNet, self).__init__(in_size, num_classes)
         self.features.add_module("init_block", ResInitBlock(in_channels=in_channels, out_channels=init_block_channels))
-        in_channels = init_block_channels
-        for i, channels_per_stage in enumerate(channels):
-            stage = nn.Sequential()
-            for j, out_channels in enumerate(channels_per_stage):
-                stride = 2 if (j == 0) and (i != 0) else 1
-                stage.add_module("unit{}".format(j + 1), CbamResUnit(in_channels=in_channels, out_channels=out_channels, stride=stride,
-                                                                     bottleneck=bottleneck))
-                in_channels = out_channels
-            self.features.add_module("stage{}".format(i + 1), stage)
-        self.features.add_module("final_pool", AvgPool2dNHWC(kernel_size=7, stride=1, fp32_out=True))
-        self.output = LinearHead(in_features=in_channels, out_features=num_classes)
-        init_conv_params(self)
-
-    def forward(self, x):
-        return run_net(self, x, self.output)
+        self.finish(add_stages(
+            self.features, init_block_channels, channels,
+            make_unit=lambda cin, cout, stride, i, j: CbamResUnit(in_channels=cin, out_channels=cout, stride=stride,
+                                                                  bottleneck=bottleneck)))
 
 
 def get_resnet(blocks, model_name=None, pretrained=False, root=DEFAULT_ROOT, **kwargs):
     """CBAM-ResNet of a depth (the reference's factory and its name, cbamresnet.py:256-325)."""
-    layers = {18: [2, 2, 2, 2], 34: [3, 4, 6, 3], 50: [3, 4, 6, 3], 101: [3, 4, 23, 3], 152: [3, 8, 36, 3]}.get(blocks)
-    if layers is None:
-        raise ValueError("Unsupported CBAM-ResNet with number of blocks: {}".format(blocks))
     bottleneck = blocks >= 50
-    widths = [256, 512, 1024, 2048] if bottleneck else [64, 128, 256, 512]
-    channels = [[w] * n for (w, n) in zip(widths, layers)]
-    net = CbamResNet(channels=channels, init_block_channels=64, bottleneck=bottleneck, **kwargs)
+    net = CbamResNet(channels=resnet_channels(blocks, bottleneck, what="CBAM-ResNet", depths=(18, 34, 50, 101, 152)),
+                     init_block_channels=64, bottleneck=bottleneck, **kwargs)
     return maybe_load_pretrained(net, model_name, pretrained, root)
 
 
-def cbam_resnet18(**kwargs):
-    return get_resnet(blocks=18, model_name="cbam_resnet18", **kwargs)
-
-
-def cbam_resnet34(**kwargs):
-    return get_resnet(blocks=34, model_name="cbam_resnet34", **kwargs)
-
-
-def cbam_resnet50(**kwargs):
-    return get_resnet(blocks=50, model_name="cbam_resnet50", **kwargs)
-
-
-def cbam_resnet101(**kwargs):
-    return get_resnet(blocks=101, model_name="cbam_resnet101", **kwargs)
-
-
-def cbam_resnet152(**kwargs):
-    return get_resnet(blocks=152, model_name="cbam_resnet152", **kwargs)
+register_variants(__name__, get_resnet, {"cbam_resnet{}".format(n): dict(blocks=n) for n in (18, 34, 50, 101, 152)})

@@ -3,7 +3,8 @@
     with the stage's final channel count; every DenseUnit reads the leading channels of it (BatchNorm + ReLU over a channel
     prefix, pcv_bn_act with a channel pitch) and its 3x3 convolution writes the 32 new channels straight into the next
     channel slice (`y_cpitch` of the fused convolution): `torch.cat((identity, x), dim=1)` never copies. The BN + ReLU
-    between the unit's two convolutions is the 1x1's epilogue.
+    between the unit's two convolutions is the 1x1's epilogue. The net keeps its own trunk loop (not `add_stages`): every stage but
+    the first opens with a `trans{i}` block that halves the width, which a stage table of unit widths cannot say.
 """
 
 __all__ = ['DenseNet', 'densenet121', 'densenet161', 'densenet169', 'densenet201', 'DenseUnit', 'TransitionBlock',
@@ -13,7 +14,8 @@ import torch
 import torch.nn as nn
 from .common.conv import pre_conv1x1_block, pre_conv3x3_block
 from .preresnet import PreResInitBlock, PreResActivation
-from ._tail import AvgPool2dNHWC, LinearHead, run_net, maybe_load_pretrained, init_conv_params, DEFAULT_ROOT
+from ._build import ClassifierNet, register_variants
+from ._tail import AvgPool2dNHWC, maybe_load_pretrained, DEFAULT_ROOT
 from .. import engine
 
 
@@ -87,12 +89,9 @@ class DenseStage(nn.Sequential):
         return engine.NHWC(buf, x.N, x.H, x.W, ctot)
 
 
-class DenseNet(nn.Module):
+class DenseNet(ClassifierNet):
     def __init__(self, channels, init_block_channels, dropout_rate=0.0, in_channels=3, in_size=(224, 224), num_classes=1000):
-        super(DenseNet, self).__init__()
-        self.in_size = in_size
-        self.num_classes = num_classes
-        self.features = nn.Sequential()
+        super(DenseNet, self).__init__(in_size, num_classes)
         self.features.add_module("init_block", PreResInitBlock(in_channels=in_channels, out_channels=init_block_channels))
         in_channels = init_block_channels
         for i, channels_per_stage in enumerate(channels):
@@ -107,12 +106,7 @@ class DenseNet(nn.Module):
                 in_channels = out_channels
             self.features.add_module("stage{}".format(i + 1), stage)
         self.features.add_module("post_activ", PreResActivation(in_channels=in_channels))
-        self.features.add_module("final_pool", AvgPool2dNHWC(kernel_size=7, stride=1, fp32_out=True))
-        self.output = LinearHead(in_features=in_channels, out_features=num_classes)
-        init_conv_params(self)
-
-    def forward(self, x):
-        return run_net(self, x, self.output)
+        self.finish(in_channels)
 
 
 # blocks -> (init_block_channels, growth_rate, layers), reference densenet.py:204-221
@@ -137,17 +131,4 @@ def get_densenet(blocks, model_name=None, pretrained=False, root=DEFAULT_ROOT, *
     return maybe_load_pretrained(net, model_name, pretrained, root)
 
 
-def densenet121(**kwargs):
-    return get_densenet(blocks=121, model_name="densenet121", **kwargs)
-
-
-def densenet161(**kwargs):
-    return get_densenet(blocks=161, model_name="densenet161", **kwargs)
-
-
-def densenet169(**kwargs):
-    return get_densenet(blocks=169, model_name="densenet169", **kwargs)
-
-
-def densenet201(**kwargs):
-    return get_densenet(blocks=201, model_name="densenet201", **kwargs)
+register_variants(__name__, get_densenet, {"densenet{}".format(n): dict(blocks=n) for n in _VERSIONS})

@@ -13,7 +13,8 @@ from .common.activ import lambda_swish
 from .common.norm import lambda_batchnorm2d
 from .common.conv import conv1x1_block, conv3x3_block, dwconv3x3_block, dwconv5x5_block
 from .common.att import round_channels, SEBlock
-from ._tail import GlobalAvgPool2dNHWC, LinearHead, run_net, maybe_load_pretrained, init_conv_params, DEFAULT_ROOT
+from ._build import ClassifierNet, add_stages, register_variants
+from ._tail import GlobalAvgPool2dNHWC, dropout_fc_head, maybe_load_pretrained, DEFAULT_ROOT
 from .. import engine
 
 
@@ -103,54 +104,37 @@ class EffiInitBlock(nn.Module):
         return engine.boundary(self, x, self._run, stem=True)
 
 
-class EfficientNet(nn.Module):
+class EfficientNet(ClassifierNet):
     pcv_16bit = "fp16"      # the 16-bit mode "auto" resolves to for this family (engine.compute_dtype_of)
 
     def __init__(self, channels, init_block_channels, final_block_channels, kernel_sizes, strides_per_stage,
                  expansion_factors, dropout_rate=0.2, tf_mode=False, bn_eps=1e-5, in_channels=3, in_size=(224, 224),
                  num_classes=1000):
-        super(EfficientNet, self).__init__()
-        self.in_size = in_size
-        self.num_classes = num_classes
+        super(EfficientNet, self).__init__(in_size, num_classes)
         normalization = lambda_batchnorm2d(eps=bn_eps)
         activation = lambda_swish()
-        self.features = nn.Sequential()
         self.features.add_module("init_block", EffiInitBlock(in_channels=in_channels, out_channels=init_block_channels,
                                                              normalization=normalization, activation=activation,
                                                              tf_mode=tf_mode))
-        in_channels = init_block_channels
-        for i, channels_per_stage in enumerate(channels):
-            stage = nn.Sequential()
-            for j, out_channels in enumerate(channels_per_stage):
-                stride = strides_per_stage[i] if (j == 0) else 1
-                if i == 0:
-                    unit = EffiDwsConvUnit(in_channels=in_channels, out_channels=out_channels, stride=stride,
-                                           normalization=normalization, activation=activation, tf_mode=tf_mode)
-                else:
-                    unit = EffiInvResUnit(in_channels=in_channels, out_channels=out_channels,
-                                          kernel_size=kernel_sizes[i][j], stride=stride, exp_factor=expansion_factors[i][j],
-                                          se_factor=4, normalization=normalization, activation=activation, tf_mode=tf_mode)
-                stage.add_module("unit{}".format(j + 1), unit)
-                in_channels = out_channels
-            self.features.add_module("stage{}".format(i + 1), stage)
-        self.features.add_module("final_block", conv1x1_block(in_channels=in_channels, out_channels=final_block_channels,
+
+        def make_unit(cin, cout, _, i, j):
+            stride = strides_per_stage[i] if (j == 0) else 1          # the family's own stride table, not the builder's rule
+            if i == 0:
+                return EffiDwsConvUnit(in_channels=cin, out_channels=cout, stride=stride, normalization=normalization,
+                                       activation=activation, tf_mode=tf_mode)
+            return EffiInvResUnit(in_channels=cin, out_channels=cout, kernel_size=kernel_sizes[i][j], stride=stride,
+                                  exp_factor=expansion_factors[i][j], se_factor=4, normalization=normalization,
+                                  activation=activation, tf_mode=tf_mode)
+        width = add_stages(self.features, init_block_channels, channels, make_unit)
+        self.features.add_module("final_block", conv1x1_block(in_channels=width, out_channels=final_block_channels,
                                                               normalization=normalization, activation=activation))
-        in_channels = final_block_channels
-        self.features.add_module("final_pool", GlobalAvgPool2dNHWC(output_size=1, fp32_out=True))
-        self.output = nn.Sequential()
-        if dropout_rate > 0.0:
-            self.output.add_module("dropout", nn.Dropout(p=dropout_rate))      # identity at inference: never launched
-        self.output.add_module("fc", LinearHead(in_features=in_channels, out_features=num_classes))
-        init_conv_params(self)
-        engine.stamp_family_dtype(self)                    # sub-modules called on their own resolve "auto" like the net
+        self.finish(final_block_channels, head=dropout_fc_head(final_block_channels, num_classes, dropout_rate),
+                    pool=GlobalAvgPool2dNHWC(output_size=1, fp32_out=True))
 
     def _head(self, a):
         if self.training:
             raise RuntimeError("EfficientNet: the MI355X path is inference only (call net.eval())")
         return self.output.fc(a)
-
-    def forward(self, x):
-        return run_net(self, x, self._head)
 
 
 # version -> (in_size, depth_factor, width_factor, dropout_rate), reference efficientnet.py:393-440
@@ -194,22 +178,14 @@ def get_efficientnet(version, in_size, tf_mode=False, bn_eps=1e-5, model_name=No
     return maybe_load_pretrained(net, model_name, pretrained, root)
 
 
-def _variant(version, suffix):
-    name = "efficientnet_{}{}".format(version, suffix)
-    size = _VERSIONS[version][0]
-    tf = dict(tf_mode=True, bn_eps=1e-3) if suffix else {}
-
-    def factory(in_size=(size, size), **kwargs):
-        return get_efficientnet(version=version, in_size=in_size, model_name=name, **dict(tf, **kwargs))
-    factory.__name__ = name
-    factory.__doc__ = "EfficientNet-{}{} (reference efficientnet.py:496-1230).".format(
-        version.upper(), " with TF-same padding and BN eps 1e-3 ('{}' weights)".format(suffix) if suffix else "")
-    return factory
+def _variants():
+    """`efficientnet_<version>[b|c]`: the native input size as default `in_size`; the `b` / `c` weights were trained with TF-same
+    padding and BN eps 1e-3 (reference efficientnet.py:496-1230, which has no efficientnet_b8b)."""
+    for version, (size, _, _, _) in _VERSIONS.items():
+        for suffix in ("", "b", "c"):
+            if (version, suffix) != ("b8", "b"):
+                tf = dict(tf_mode=True, bn_eps=1e-3) if suffix else {}
+                yield "efficientnet_{}{}".format(version, suffix), dict(version=version, in_size=(size, size), **tf)
 
 
-for _v in _VERSIONS:
-    for _s in ("", "b", "c"):
-        if _v == "b8" and _s == "b":
-            continue                                            # the reference has no efficientnet_b8b
-        globals()["efficientnet_{}{}".format(_v, _s)] = _variant(_v, _s)
-        __all__.append("efficientnet_{}{}".format(_v, _s))
+register_variants(__name__, get_efficientnet, dict(_variants()))

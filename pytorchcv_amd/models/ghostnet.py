@@ -16,7 +16,9 @@ import torch.nn as nn
 from .common.activ import lambda_relu
 from .common.conv import conv1x1, conv1x1_block, conv3x3_block, dwconv3x3_block, dwconv5x5_block, dwsconv3x3_block
 from .common.att import round_channels, SEBlock
-from ._tail import AvgPool2dNHWC, run_net, maybe_load_pretrained, init_conv_params, DEFAULT_ROOT
+from .resnet import SkipUnit
+from ._build import ClassifierNet, add_stages, register_variants
+from ._tail import maybe_load_pretrained, DEFAULT_ROOT
 from .. import engine
 
 
@@ -77,24 +79,17 @@ class GhostExpBlock(nn.Module):
         return engine.boundary(self, x, lambda a: self._run(a, residual))
 
 
-class GhostUnit(nn.Module):
+class GhostUnit(SkipUnit):
     """GhostNet unit (reference ghostnet.py:124-174): body + identity, the identity a depthwise-separable 3x3 block where the shape
-    changes. The add is the epilogue of the body's last launch."""
+    changes. The add is the epilogue of the body's last launch; there is no activation behind it."""
     def __init__(self, in_channels, out_channels, stride, use_kernel3, exp_factor, use_se):
         super(GhostUnit, self).__init__()
-        self.resize_identity = (in_channels != out_channels) or (stride != 1)
         self.body = GhostExpBlock(in_channels=in_channels, out_channels=out_channels, stride=stride, use_kernel3=use_kernel3,
                                   exp_factor=exp_factor, use_se=use_se)
-        if self.resize_identity:
-            self.identity_conv = dwsconv3x3_block(in_channels=in_channels, out_channels=out_channels, stride=stride,
-                                                  pw_activation=None)
+        self.add_skip(in_channels, out_channels, stride, block=dwsconv3x3_block, activation=None, pw_activation=None)
 
     def _run(self, a):
-        identity = self.identity_conv(a) if self.resize_identity else a
-        return self.body(a, residual=identity)
-
-    def forward(self, x):
-        return engine.boundary(self, x, self._run)
+        return self.body(a, residual=self._identity(a))
 
 
 class GhostClassifier(nn.Module):
@@ -111,42 +106,28 @@ class GhostClassifier(nn.Module):
         return engine.boundary(self, x, self._run)
 
 
-class GhostNet(nn.Module):
+class GhostNet(ClassifierNet):
     """`features` (init_block, stage1..5 of unit1..n, final_block, final_pool) + `output` classifier (reference ghostnet.py:209-302)."""
     pcv_16bit = "fp16"      # the 16-bit mode "auto" resolves to for this family (engine.compute_dtype_of; DESIGN.md section 3)
 
     def __init__(self, channels, init_block_channels, final_block_channels, classifier_mid_channels, kernels3, exp_factors, use_se,
                  first_stride, in_channels=3, in_size=(224, 224), num_classes=1000):
-        super(GhostNet, self).__init__()
-        self.in_size = in_size
-        self.num_classes = num_classes
-        self.features = nn.Sequential()
+        super(GhostNet, self).__init__(in_size, num_classes)
         self.features.add_module("init_block", conv3x3_block(in_channels=in_channels, out_channels=init_block_channels, stride=2))
-        in_channels = init_block_channels
-        for i, channels_per_stage in enumerate(channels):
-            stage = nn.Sequential()
-            for j, out_channels in enumerate(channels_per_stage):
-                stride = 2 if (j == 0) and ((i != 0) or first_stride) else 1
-                stage.add_module("unit{}".format(j + 1), GhostUnit(
-                    in_channels=in_channels, out_channels=out_channels, stride=stride, use_kernel3=(kernels3[i][j] == 1),
-                    exp_factor=exp_factors[i][j], use_se=(use_se[i][j] == 1)))
-                in_channels = out_channels
-            self.features.add_module("stage{}".format(i + 1), stage)
-        self.features.add_module("final_block", conv1x1_block(in_channels=in_channels, out_channels=final_block_channels))
-        in_channels = final_block_channels
-        self.features.add_module("final_pool", AvgPool2dNHWC(kernel_size=7, stride=1, fp32_out=True))
-        self.output = GhostClassifier(in_channels=in_channels, out_channels=num_classes, mid_channels=classifier_mid_channels)
-        init_conv_params(self)
-        engine.stamp_family_dtype(self)                    # sub-modules called on their own resolve "auto" like the net
+        width = add_stages(
+            self.features, init_block_channels, channels, downsample_first=first_stride,
+            make_unit=lambda cin, cout, stride, i, j: GhostUnit(
+                in_channels=cin, out_channels=cout, stride=stride, use_kernel3=(kernels3[i][j] == 1),
+                exp_factor=exp_factors[i][j], use_se=(use_se[i][j] == 1)))
+        self.features.add_module("final_block", conv1x1_block(in_channels=width, out_channels=final_block_channels))
+        self.finish(final_block_channels, head=GhostClassifier(in_channels=final_block_channels, out_channels=num_classes,
+                                                               mid_channels=classifier_mid_channels))
 
     def _head(self, a):
         if a.H != 1 or a.W != 1:
             raise RuntimeError("classifier expects a 1x1 pooled map, got {}x{}".format(a.H, a.W))
         y = self.output(a)
         return y.t.view(y.N, -1)
-
-    def forward(self, x):
-        return run_net(self, x, self._head)
 
 
 def get_ghostnet(width_scale=1.0, model_name=None, pretrained=False, root=DEFAULT_ROOT, **kwargs):
@@ -169,6 +150,4 @@ def get_ghostnet(width_scale=1.0, model_name=None, pretrained=False, root=DEFAUL
     return maybe_load_pretrained(net, model_name, pretrained, root)
 
 
-def ghostnet(**kwargs):
-    """GhostNet 1.0x (reference ghostnet.py:367-385)."""
-    return get_ghostnet(model_name="ghostnet", **kwargs)
+register_variants(__name__, get_ghostnet, {"ghostnet": {}})       # GhostNet 1.0x (reference ghostnet.py:367-385)

@@ -10,7 +10,8 @@
     `FUSED = False` selects the composed path instead - `engine.interpolate` + `engine.add`, one launch per upsample and per add,
     partial sums rounded to the storage type like the reference's own tensors. It is also what runs where pcv_hr_fuse_supported
     refuses a shape (a map that does not divide, a scale factor that is no power of two), the baseline of tests/tools/bench_hrnet.py
-    and a cross-check in tests: in fp32 both paths give the same bits.
+    and a cross-check in tests: in fp32 both paths give the same bits. The net keeps its own trunk loop (not `add_stages`): a
+    stage is one multi-branch HRStage that takes and returns a list of maps, not a sequence of units.
 """
 
 __all__ = ['HRNet', 'hrnet_w18_small_v1', 'hrnet_w18_small_v2', 'hrnetv2_w18', 'hrnetv2_w30', 'hrnetv2_w32', 'hrnetv2_w40',
@@ -21,7 +22,8 @@ import torch
 import torch.nn as nn
 from .common.conv import conv1x1_block, conv3x3_block
 from .resnet import ResUnit, ResStage
-from ._tail import AvgPool2dNHWC, LinearHead, run_net, maybe_load_pretrained, init_conv_params, DEFAULT_ROOT
+from ._build import ClassifierNet, register_variants
+from ._tail import maybe_load_pretrained, DEFAULT_ROOT
 from .. import engine
 
 FUSED = True      # module-level switch: False = every exchange through engine.interpolate + engine.add (see the module docstring)
@@ -246,16 +248,12 @@ class HRFinalBlock(nn.Module):
         return _on_handles(self, x, self._run)
 
 
-class HRNet(nn.Module):
+class HRNet(ClassifierNet):
     """`features` (init_block, stage1..3, final_block, final_pool) + `output` Linear (reference hrnet.py:299-379)."""
     def __init__(self, channels, init_block_channels, init_num_subblocks, num_modules, num_subblocks, in_channels=3,
                  in_size=(224, 224), num_classes=1000):
-        super(HRNet, self).__init__()
-        self.in_size = in_size
-        self.num_classes = num_classes
+        super(HRNet, self).__init__(in_size, num_classes)
         self.branches = [2, 3, 4]
-
-        self.features = nn.Sequential()
         self.features.add_module("init_block", HRInitBlock(in_channels=in_channels, out_channels=init_block_channels, mid_channels=64,
                                                            num_subblocks=init_num_subblocks))
         in_channels_list = [init_block_channels]
@@ -265,12 +263,7 @@ class HRNet(nn.Module):
                 num_branches=self.branches[i], num_subblocks=num_subblocks[i]))
             in_channels_list = self.features[-1].in_channels_list
         self.features.add_module("final_block", HRFinalBlock(in_channels_list=in_channels_list, out_channels_list=[128, 256, 512, 1024]))
-        self.features.add_module("final_pool", AvgPool2dNHWC(kernel_size=7, stride=1, fp32_out=True))
-        self.output = LinearHead(in_features=2048, out_features=num_classes)
-        init_conv_params(self)
-
-    def forward(self, x):
-        return run_net(self, x, self.output)
+        self.finish(2048)
 
 
 def get_hrnet(version, model_name=None, pretrained=False, root=DEFAULT_ROOT, **kwargs):
@@ -292,46 +285,7 @@ def get_hrnet(version, model_name=None, pretrained=False, root=DEFAULT_ROOT, **k
     return maybe_load_pretrained(net, model_name, pretrained, root)
 
 
-def hrnet_w18_small_v1(**kwargs):
-    """HRNet-W18 Small V1 (reference hrnet.py:476-491)."""
-    return get_hrnet(version="w18s1", model_name="hrnet_w18_small_v1", **kwargs)
-
-
-def hrnet_w18_small_v2(**kwargs):
-    """HRNet-W18 Small V2."""
-    return get_hrnet(version="w18s2", model_name="hrnet_w18_small_v2", **kwargs)
-
-
-def hrnetv2_w18(**kwargs):
-    """HRNetV2-W18."""
-    return get_hrnet(version="w18", model_name="hrnetv2_w18", **kwargs)
-
-
-def hrnetv2_w30(**kwargs):
-    """HRNetV2-W30."""
-    return get_hrnet(version="w30", model_name="hrnetv2_w30", **kwargs)
-
-
-def hrnetv2_w32(**kwargs):
-    """HRNetV2-W32."""
-    return get_hrnet(version="w32", model_name="hrnetv2_w32", **kwargs)
-
-
-def hrnetv2_w40(**kwargs):
-    """HRNetV2-W40."""
-    return get_hrnet(version="w40", model_name="hrnetv2_w40", **kwargs)
-
-
-def hrnetv2_w44(**kwargs):
-    """HRNetV2-W44."""
-    return get_hrnet(version="w44", model_name="hrnetv2_w44", **kwargs)
-
-
-def hrnetv2_w48(**kwargs):
-    """HRNetV2-W48."""
-    return get_hrnet(version="w48", model_name="hrnetv2_w48", **kwargs)
-
-
-def hrnetv2_w64(**kwargs):
-    """HRNetV2-W64."""
-    return get_hrnet(version="w64", model_name="hrnetv2_w64", **kwargs)
+# HRNet-W18 Small V1 / V2 and HRNetV2-W18 .. W64 (reference hrnet.py:476-635)
+register_variants(__name__, get_hrnet, dict(
+    [("hrnet_w18_small_v1", dict(version="w18s1")), ("hrnet_w18_small_v2", dict(version="w18s2"))] +
+    [("hrnetv2_w{}".format(w), dict(version="w{}".format(w))) for w in (18, 30, 32, 40, 44, 48, 64)]))

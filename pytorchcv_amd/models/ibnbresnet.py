@@ -9,8 +9,8 @@ __all__ = ['IBNbResNet', 'ibnb_resnet50', 'ibnb_resnet101', 'ibnb_resnet152', 'I
            'IBNbResUnit', 'IBNbResInitBlock', 'get_ibnbresnet']
 
 import torch.nn as nn
-from .resnet import ResStage, ResUnit
-from ._build import ClassifierNet, add_stages, stage_table
+from .resnet import ResStage, ResUnit, resnet_channels
+from ._build import ClassifierNet, add_stages, register_variants
 from ._tail import MaxPool2dNHWC, maybe_load_pretrained, DEFAULT_ROOT
 from .. import engine
 
@@ -56,8 +56,7 @@ class IBNbResUnit(ResUnit):
         self._pcv_in = None
 
     def _norm_tail(self, a, y):
-        identity = self.identity_conv(a) if self.resize_identity else a
-        z = self.body.conv3(y, residual=identity, post_act=None)
+        z = self.body.conv3(y, residual=self._identity(a), post_act=None)
         if self._pcv_in is None:
             self._pcv_in = engine.InstNormRunner(self.inst_norm)
         return self._pcv_in.run(z, engine.act_code(self.activ))
@@ -101,26 +100,12 @@ class IBNbResNet(ClassifierNet):
                                in_channels=cin, out_channels=cout, stride=stride,
                                use_inst_norm=(i < 2) and (j == len(channels[i]) - 1)))
         self.finish(width)
-        engine.stamp_family_dtype(self)                    # sub-modules called on their own resolve "auto" like the net
-
-
-_DEPTHS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}
 
 
 def get_ibnbresnet(blocks, model_name=None, pretrained=False, root=DEFAULT_ROOT, **kwargs):
-    if blocks not in _DEPTHS:
-        raise ValueError("Unsupported IBN(b)-ResNet with number of blocks: {}".format(blocks))
-    net = IBNbResNet(channels=stage_table((256, 512, 1024, 2048), _DEPTHS[blocks]), init_block_channels=64, **kwargs)
+    net = IBNbResNet(channels=resnet_channels(blocks, True, what="IBN(b)-ResNet", depths=(50, 101, 152)), init_block_channels=64,
+                     **kwargs)
     return maybe_load_pretrained(net, model_name, pretrained, root)
 
 
-def ibnb_resnet50(**kwargs):
-    return get_ibnbresnet(blocks=50, model_name="ibnb_resnet50", **kwargs)
-
-
-def ibnb_resnet101(**kwargs):
-    return get_ibnbresnet(blocks=101, model_name="ibnb_resnet101", **kwargs)
-
-
-def ibnb_resnet152(**kwargs):
-    return get_ibnbresnet(blocks=152, model_name="ibnb_resnet152", **kwargs)
+register_variants(__name__, get_ibnbresnet, {"ibnb_resnet{}".format(n): dict(blocks=n) for n in (50, 101, 152)})

@@ -16,8 +16,8 @@ __all__ = ['IBNResNet', 'ibn_resnet50', 'ibn_resnet101', 'ibn_resnet152', 'ibn_c
 import torch.nn as nn
 from .common.norm import IBN
 from .common.conv import conv1x1_block, conv3x3_block
-from .resnet import ResInitBlock, ResStage, ResUnit
-from ._build import ClassifierNet, add_stages, stage_table
+from .resnet import SkipUnit, ResInitBlock, ResStage, ResUnit, resnet_channels
+from ._build import ClassifierNet, add_stages, register_variants
 from ._tail import maybe_load_pretrained, DEFAULT_ROOT
 from .. import engine
 
@@ -70,22 +70,12 @@ class IBNResBottleneck(nn.Module):
         return engine.boundary(self, x, lambda a: self.conv3(self.conv2(self.conv1(a)), residual=residual, post_act=post_act))
 
 
-class IBNResUnit(nn.Module):
+class IBNResUnit(SkipUnit):
     """relu(body(x) + identity) (reference ibnresnet.py:168-212). Not chainable: see the module docstring."""
     def __init__(self, in_channels, out_channels, stride, conv1_ibn):
         super(IBNResUnit, self).__init__()
-        self.resize_identity = (in_channels != out_channels) or (stride != 1)
         self.body = IBNResBottleneck(in_channels=in_channels, out_channels=out_channels, stride=stride, conv1_ibn=conv1_ibn)
-        if self.resize_identity:
-            self.identity_conv = conv1x1_block(in_channels=in_channels, out_channels=out_channels, stride=stride, activation=None)
-        self.activ = nn.ReLU(inplace=True)
-
-    def _run(self, a):
-        identity = self.identity_conv(a) if self.resize_identity else a
-        return self.body(a, residual=identity, post_act=self.activ)
-
-    def forward(self, x):
-        return engine.boundary(self, x, self._run)
+        self.add_skip(in_channels, out_channels, stride)
 
 
 def ibn_unit(in_channels, out_channels, stride):
@@ -105,26 +95,11 @@ class IBNResNet(ClassifierNet):
         width = add_stages(self.features, init_block_channels, channels, container=ResStage,
                            make_unit=lambda cin, cout, stride, i, j: ibn_unit(cin, cout, stride))
         self.finish(width)
-        engine.stamp_family_dtype(self)                    # sub-modules called on their own resolve "auto" like the net
-
-
-_DEPTHS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}
 
 
 def get_ibnresnet(blocks, model_name=None, pretrained=False, root=DEFAULT_ROOT, **kwargs):
-    if blocks not in _DEPTHS:
-        raise ValueError("Unsupported IBN-ResNet with number of blocks: {}".format(blocks))
-    net = IBNResNet(channels=stage_table((256, 512, 1024, 2048), _DEPTHS[blocks]), init_block_channels=64, **kwargs)
+    net = IBNResNet(channels=resnet_channels(blocks, True, what="IBN-ResNet", depths=(50, 101, 152)), init_block_channels=64, **kwargs)
     return maybe_load_pretrained(net, model_name, pretrained, root)
 
 
-def ibn_resnet50(**kwargs):
-    return get_ibnresnet(blocks=50, model_name="ibn_resnet50", **kwargs)
-
-
-def ibn_resnet101(**kwargs):
-    return get_ibnresnet(blocks=101, model_name="ibn_resnet101", **kwargs)
-
-
-def ibn_resnet152(**kwargs):
-    return get_ibnresnet(blocks=152, model_name="ibn_resnet152", **kwargs)
+register_variants(__name__, get_ibnresnet, {"ibn_resnet{}".format(n): dict(blocks=n) for n in (50, 101, 152)})

@@ -10,10 +10,10 @@ __all__ = ['IBNResNeXt', 'ibn_resnext50_32x4d', 'ibn_resnext101_32x4d', 'ibn_res
 import math
 import torch.nn as nn
 from .common.conv import conv1x1_block, conv3x3_block
-from .resnet import ResInitBlock, ResStage
+from .resnet import SkipUnit, ResInitBlock, ResStage, resnet_channels
 from .resnext import ResNeXtUnit
 from .ibnresnet import ibn_conv1x1_block
-from ._build import ClassifierNet, add_stages, stage_table
+from ._build import ClassifierNet, add_stages, register_variants
 from ._tail import maybe_load_pretrained, DEFAULT_ROOT
 from .. import engine
 
@@ -33,23 +33,13 @@ class IBNResNeXtBottleneck(nn.Module):
         return engine.boundary(self, x, lambda a: self.conv3(self.conv2(self.conv1(a)), residual=residual, post_act=post_act))
 
 
-class IBNResNeXtUnit(nn.Module):
+class IBNResNeXtUnit(SkipUnit):
     """relu(body(x) + identity) (reference ibnresnext.py:68-120); not chainable, as IBNResUnit."""
     def __init__(self, in_channels, out_channels, stride, cardinality, bottleneck_width, conv1_ibn):
         super(IBNResNeXtUnit, self).__init__()
-        self.resize_identity = (in_channels != out_channels) or (stride != 1)
         self.body = IBNResNeXtBottleneck(in_channels=in_channels, out_channels=out_channels, stride=stride,
                                          cardinality=cardinality, bottleneck_width=bottleneck_width, conv1_ibn=conv1_ibn)
-        if self.resize_identity:
-            self.identity_conv = conv1x1_block(in_channels=in_channels, out_channels=out_channels, stride=stride, activation=None)
-        self.activ = nn.ReLU(inplace=True)
-
-    def _run(self, a):
-        identity = self.identity_conv(a) if self.resize_identity else a
-        return self.body(a, residual=identity, post_act=self.activ)
-
-    def forward(self, x):
-        return engine.boundary(self, x, self._run)
+        self.add_skip(in_channels, out_channels, stride)
 
 
 class IBNResNeXt(ClassifierNet):
@@ -69,27 +59,15 @@ class IBNResNeXt(ClassifierNet):
                                bottleneck_width=bottleneck_width)
         width = add_stages(self.features, init_block_channels, channels, container=ResStage, make_unit=make_unit)
         self.finish(width)
-        engine.stamp_family_dtype(self)                    # sub-modules called on their own resolve "auto" like the net
-
-
-_DEPTHS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3)}
 
 
 def get_ibnresnext(blocks, cardinality, bottleneck_width, model_name=None, pretrained=False, root=DEFAULT_ROOT, **kwargs):
-    if blocks not in _DEPTHS:
-        raise ValueError("Unsupported IBN-ResNeXt with number of blocks: {}".format(blocks))
-    net = IBNResNeXt(channels=stage_table((256, 512, 1024, 2048), _DEPTHS[blocks]), init_block_channels=64,
+    net = IBNResNeXt(channels=resnet_channels(blocks, True, what="IBN-ResNeXt", depths=(50, 101)), init_block_channels=64,
                      cardinality=cardinality, bottleneck_width=bottleneck_width, **kwargs)
     return maybe_load_pretrained(net, model_name, pretrained, root)
 
 
-def ibn_resnext50_32x4d(**kwargs):
-    return get_ibnresnext(blocks=50, cardinality=32, bottleneck_width=4, model_name="ibn_resnext50_32x4d", **kwargs)
-
-
-def ibn_resnext101_32x4d(**kwargs):
-    return get_ibnresnext(blocks=101, cardinality=32, bottleneck_width=4, model_name="ibn_resnext101_32x4d", **kwargs)
-
-
-def ibn_resnext101_64x4d(**kwargs):
-    return get_ibnresnext(blocks=101, cardinality=64, bottleneck_width=4, model_name="ibn_resnext101_64x4d", **kwargs)
+register_variants(__name__, get_ibnresnext, {
+    "ibn_resnext50_32x4d": dict(blocks=50, cardinality=32, bottleneck_width=4),
+    "ibn_resnext101_32x4d": dict(blocks=101, cardinality=32, bottleneck_width=4),
+    "ibn_resnext101_64x4d": dict(blocks=101, cardinality=64, bottleneck_width=4)})

@@ -16,7 +16,8 @@ from .common.activ import lambda_relu, lambda_swish, create_activation_layer
 from .common.norm import lambda_batchnorm2d, create_normalization_layer
 from .common.conv import conv1x1_block, conv3x3_block, dwconv3x3_block, mbconv_chain
 from .common.att import round_channels, SEBlock
-from ._tail import AvgPool2dNHWC, LinearHead, run_net, maybe_load_pretrained, init_conv_params, DEFAULT_ROOT
+from ._build import ClassifierNet, add_stages, register_variants
+from ._tail import maybe_load_pretrained, DEFAULT_ROOT
 from .. import engine
 
 
@@ -194,38 +195,25 @@ class MixInitBlock(nn.Module):
         return engine.boundary(self, x, self._run, stem=True)
 
 
-class MixNet(nn.Module):
+class MixNet(ClassifierNet):
     """`features` (init_block, stage1..4 of unit1..n, final_block, final_pool) + `output` Linear (reference mixnet.py:332-429)."""
     pcv_16bit = "fp16"      # the 16-bit mode "auto" resolves to for this family (engine.compute_dtype_of; DESIGN.md section 3)
 
     def __init__(self, channels, init_block_channels, final_block_channels, exp_kernel_counts, conv1_kernel_counts,
                  conv2_kernel_counts, exp_factors, se_factors, in_channels=3, in_size=(224, 224), num_classes=1000):
-        super(MixNet, self).__init__()
-        self.in_size = in_size
-        self.num_classes = num_classes
-        self.features = nn.Sequential()
+        super(MixNet, self).__init__(in_size, num_classes)
         self.features.add_module("init_block", MixInitBlock(in_channels=in_channels, out_channels=init_block_channels))
-        in_channels = init_block_channels
-        for i, channels_per_stage in enumerate(channels):
-            stage = nn.Sequential()
-            for j, out_channels in enumerate(channels_per_stage):
-                stride = 2 if ((j == 0) and (i != 3)) or ((j == len(channels_per_stage) // 2) and (i == 3)) else 1
-                activation = lambda_relu() if i == 0 else lambda_swish()
-                stage.add_module("unit{}".format(j + 1), MixUnit(
-                    in_channels=in_channels, out_channels=out_channels, stride=stride, exp_kernel_count=exp_kernel_counts[i][j],
-                    conv1_kernel_count=conv1_kernel_counts[i][j], conv2_kernel_count=conv2_kernel_counts[i][j],
-                    exp_factor=exp_factors[i][j], se_factor=se_factors[i][j], activation=activation))
-                in_channels = out_channels
-            self.features.add_module("stage{}".format(i + 1), stage)
-        self.features.add_module("final_block", conv1x1_block(in_channels=in_channels, out_channels=final_block_channels))
-        in_channels = final_block_channels
-        self.features.add_module("final_pool", AvgPool2dNHWC(kernel_size=7, stride=1, fp32_out=True))
-        self.output = LinearHead(in_features=in_channels, out_features=num_classes)
-        init_conv_params(self)
-        engine.stamp_family_dtype(self)                    # sub-modules called on their own resolve "auto" like the net
 
-    def forward(self, x):
-        return run_net(self, x, self.output)
+        def make_unit(cin, cout, _, i, j):
+            # the family's own stride rule: every stage opens with stride 2, but the fourth has it in its middle
+            stride = 2 if ((j == 0) and (i != 3)) or ((j == len(channels[i]) // 2) and (i == 3)) else 1
+            return MixUnit(in_channels=cin, out_channels=cout, stride=stride, exp_kernel_count=exp_kernel_counts[i][j],
+                           conv1_kernel_count=conv1_kernel_counts[i][j], conv2_kernel_count=conv2_kernel_counts[i][j],
+                           exp_factor=exp_factors[i][j], se_factor=se_factors[i][j],
+                           activation=(lambda_relu() if i == 0 else lambda_swish()))
+        width = add_stages(self.features, init_block_channels, channels, make_unit)
+        self.features.add_module("final_block", conv1x1_block(in_channels=width, out_channels=final_block_channels))
+        self.finish(final_block_channels)
 
 
 def get_mixnet(version, width_scale, model_name=None, pretrained=False, root=DEFAULT_ROOT, **kwargs):
@@ -258,16 +246,6 @@ def get_mixnet(version, width_scale, model_name=None, pretrained=False, root=DEF
     return maybe_load_pretrained(net, model_name, pretrained, root)
 
 
-def mixnet_s(**kwargs):
-    """MixNet-S (reference mixnet.py:507-527)."""
-    return get_mixnet(version="s", width_scale=1.0, model_name="mixnet_s", **kwargs)
-
-
-def mixnet_m(**kwargs):
-    """MixNet-M (reference mixnet.py:530-550)."""
-    return get_mixnet(version="m", width_scale=1.0, model_name="mixnet_m", **kwargs)
-
-
-def mixnet_l(**kwargs):
-    """MixNet-L: MixNet-M at width 1.3 (reference mixnet.py:553-573)."""
-    return get_mixnet(version="m", width_scale=1.3, model_name="mixnet_l", **kwargs)
+# MixNet-S, -M and -L = MixNet-M at width 1.3 (reference mixnet.py:507-573)
+register_variants(__name__, get_mixnet, {"mixnet_s": dict(version="s", width_scale=1.0), "mixnet_m": dict(version="m", width_scale=1.0),
+                                         "mixnet_l": dict(version="m", width_scale=1.3)})

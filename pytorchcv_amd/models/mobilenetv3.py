@@ -13,7 +13,8 @@ import torch.nn as nn
 from .common.activ import lambda_relu, lambda_hswish, lambda_hsigmoid, HSwish
 from .common.conv import conv1x1, conv1x1_block, conv3x3_block, dwconv3x3_block, dwconv5x5_block, mbconv_chain
 from .common.att import SEBlock, round_channels
-from ._tail import AvgPool2dNHWC, run_net, maybe_load_pretrained, init_conv_params, DEFAULT_ROOT
+from ._build import ClassifierNet, add_stages, register_variants
+from ._tail import maybe_load_pretrained, DEFAULT_ROOT
 from .. import engine
 
 
@@ -86,45 +87,29 @@ class MobileNetV3Classifier(nn.Module):
         return self.conv2(y, out_fp32=True)
 
 
-class MobileNetV3(nn.Module):
+class MobileNetV3(ClassifierNet):
     pcv_16bit = "fp16"      # the 16-bit mode "auto" resolves to for this family (engine.compute_dtype_of)
 
     def __init__(self, channels, exp_channels, init_block_channels, final_block_channels, classifier_mid_channels, kernels3,
                  use_relu, use_se, first_stride, final_use_se, in_channels=3, in_size=(224, 224), num_classes=1000):
-        super(MobileNetV3, self).__init__()
-        self.in_size = in_size
-        self.num_classes = num_classes
-        self.features = nn.Sequential()
+        super(MobileNetV3, self).__init__(in_size, num_classes)
         self.features.add_module("init_block", conv3x3_block(in_channels=in_channels, out_channels=init_block_channels,
                                                              stride=2, activation=lambda_hswish()))
-        in_channels = init_block_channels
-        for i, channels_per_stage in enumerate(channels):
-            stage = nn.Sequential()
-            for j, out_channels in enumerate(channels_per_stage):
-                stride = 2 if (j == 0) and ((i != 0) or first_stride) else 1
-                stage.add_module("unit{}".format(j + 1), MobileNetV3Unit(
-                    in_channels=in_channels, out_channels=out_channels, exp_channels=exp_channels[i][j],
-                    use_kernel3=(kernels3[i][j] == 1), stride=stride,
-                    activation=(lambda_relu() if use_relu[i][j] == 1 else lambda_hswish()), use_se=(use_se[i][j] == 1)))
-                in_channels = out_channels
-            self.features.add_module("stage{}".format(i + 1), stage)
-        self.features.add_module("final_block", MobileNetV3FinalBlock(in_channels=in_channels, out_channels=final_block_channels,
+        width = add_stages(
+            self.features, init_block_channels, channels, downsample_first=first_stride,
+            make_unit=lambda cin, cout, stride, i, j: MobileNetV3Unit(
+                in_channels=cin, out_channels=cout, exp_channels=exp_channels[i][j], use_kernel3=(kernels3[i][j] == 1), stride=stride,
+                activation=(lambda_relu() if use_relu[i][j] == 1 else lambda_hswish()), use_se=(use_se[i][j] == 1)))
+        self.features.add_module("final_block", MobileNetV3FinalBlock(in_channels=width, out_channels=final_block_channels,
                                                                       use_se=final_use_se))
-        in_channels = final_block_channels
-        self.features.add_module("final_pool", AvgPool2dNHWC(kernel_size=7, stride=1, fp32_out=True))
-        self.output = MobileNetV3Classifier(in_channels=in_channels, out_channels=num_classes,
-                                            mid_channels=classifier_mid_channels, dropout_rate=0.2)
-        init_conv_params(self)
-        engine.stamp_family_dtype(self)                    # sub-modules called on their own resolve "auto" like the net
+        self.finish(final_block_channels, head=MobileNetV3Classifier(
+            in_channels=final_block_channels, out_channels=num_classes, mid_channels=classifier_mid_channels, dropout_rate=0.2))
 
     def _head(self, a):
         if a.H != 1 or a.W != 1:
             raise RuntimeError("classifier expects a 1x1 pooled map, got {}x{}".format(a.H, a.W))
         y = self.output(a)
         return y.t.view(y.N, -1)
-
-    def forward(self, x):
-        return run_net(self, x, self._head)
 
 
 # (channels, exp_channels, kernels3, use_relu, use_se, first_stride, final_block_channels) - reference mobilenetv3.py:311-332
@@ -159,16 +144,6 @@ def get_mobilenetv3(version, width_scale, model_name=None, pretrained=False, roo
     return maybe_load_pretrained(net, model_name, pretrained, root)
 
 
-def _variant(version, tag, width_scale):
-    name = "mobilenetv3_{}_{}".format(version, tag)
-
-    def factory(**kwargs):
-        return get_mobilenetv3(version=version, width_scale=width_scale, model_name=name, **kwargs)
-    factory.__name__ = name
-    factory.__doc__ = "MobileNetV3 {} x{} (reference mobilenetv3.py:367-595).".format(version, width_scale)
-    return factory
-
-
-for _version in ("small", "large"):
-    for _tag, _scale in (("w7d20", 0.35), ("wd2", 0.5), ("w3d4", 0.75), ("w1", 1.0), ("w5d4", 1.25)):
-        globals()["mobilenetv3_{}_{}".format(_version, _tag)] = _variant(_version, _tag, _scale)
+register_variants(__name__, get_mobilenetv3, {
+    "mobilenetv3_{}_{}".format(version, tag): dict(version=version, width_scale=scale)
+    for version in ("small", "large") for tag, scale in (("w7d20", 0.35), ("wd2", 0.5), ("w3d4", 0.75), ("w1", 1.0), ("w5d4", 1.25))})

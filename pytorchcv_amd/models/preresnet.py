@@ -14,8 +14,9 @@ __all__ = ['PreResNet', 'preresnet10', 'preresnet12', 'preresnet14', 'preresnetb
 import torch.nn as nn
 from .common.norm import lambda_batchnorm2d
 from .common.conv import pre_conv1x1_block, pre_conv3x3_block, conv1x1
-from .resnet import resnet_layers
-from ._tail import MaxPool2dNHWC, AvgPool2dNHWC, LinearHead, run_net, maybe_load_pretrained, init_conv_params, DEFAULT_ROOT
+from .resnet import SkipUnit, resnet_channels, RESNET_DEPTHS
+from ._build import ClassifierNet, add_stages, register_variants
+from ._tail import MaxPool2dNHWC, maybe_load_pretrained, DEFAULT_ROOT
 from .. import engine
 
 
@@ -72,30 +73,26 @@ def _run_body(body, x):
     return engine.boundary(body, x, run)               # (tensor entry: the module's resolved type + the fp16 range guard)
 
 
-class PreResUnit(nn.Module):
+class PreResUnit(SkipUnit):
     """Pre-activation residual unit (reference preresnet.py:109-164): the identity convolution, when present, reads the
     pre-activated input and has neither BN nor activation."""
     def __init__(self, in_channels, out_channels, stride, bias=False, normalization=lambda_batchnorm2d(), bottleneck=True,
                  conv1_stride=False):
         super(PreResUnit, self).__init__()
-        self.resize_identity = (in_channels != out_channels) or (stride != 1)
         if bottleneck:
             self.body = PreResBottleneck(in_channels=in_channels, out_channels=out_channels, stride=stride,
                                          conv1_stride=conv1_stride)
         else:
             self.body = PreResBlock(in_channels=in_channels, out_channels=out_channels, stride=stride, bias=bias,
                                     normalization=normalization)
-        if self.resize_identity:
-            self.identity_conv = conv1x1(in_channels=in_channels, out_channels=out_channels, stride=stride, bias=bias)
+        self.add_skip(in_channels, out_channels, stride, block=conv1x1, activation=None, bias=bias)
 
-    def _run(self, a):
+    def _run(self, a, se=None):
+        """`se`: the SEBlock between the body and the add (SEPreResUnit runs this function with its own)."""
         blocks = self.body.chain()
         pre = blocks[0].preact(a)
         identity = self.identity_conv(pre) if self.resize_identity else a
-        return _chain_forward(blocks, pre, residual=identity)
-
-    def forward(self, x):
-        return engine.boundary(self, x, self._run)
+        return _chain_forward(blocks, pre, residual=identity, se=se)
 
 
 class PreResInitBlock(nn.Module):
@@ -137,31 +134,19 @@ class PreResActivation(nn.Module):
         return engine.boundary(self, x, self._run)
 
 
-class PreResNet(nn.Module):
+class PreResNet(ClassifierNet):
+    unit = PreResUnit            # (SE-PreResNet is this net with its own unit)
+
     def __init__(self, channels, init_block_channels, bottleneck, conv1_stride, in_channels=3, in_size=(224, 224),
                  num_classes=1000):
-        super(PreResNet, self).__init__()
-        self.in_size = in_size
-        self.num_classes = num_classes
-        self.features = nn.Sequential()
+        super(PreResNet, self).__init__(in_size, num_classes)
         self.features.add_module("init_block", PreResInitBlock(in_channels=in_channels, out_channels=init_block_channels))
-        in_channels = init_block_channels
-        for i, channels_per_stage in enumerate(channels):
-            stage = nn.Sequential()
-            for j, out_channels in enumerate(channels_per_stage):
-                stride = 1 if (i == 0) or (j != 0) else 2
-                stage.add_module("unit{}".format(j + 1), PreResUnit(in_channels=in_channels, out_channels=out_channels,
-                                                                   stride=stride, bottleneck=bottleneck,
-                                                                   conv1_stride=conv1_stride))
-                in_channels = out_channels
-            self.features.add_module("stage{}".format(i + 1), stage)
-        self.features.add_module("post_activ", PreResActivation(in_channels=in_channels))
-        self.features.add_module("final_pool", AvgPool2dNHWC(kernel_size=7, stride=1, fp32_out=True))
-        self.output = LinearHead(in_features=in_channels, out_features=num_classes)
-        init_conv_params(self)
-
-    def forward(self, x):
-        return run_net(self, x, self.output)
+        width = add_stages(
+            self.features, init_block_channels, channels,
+            make_unit=lambda cin, cout, stride, i, j: self.unit(in_channels=cin, out_channels=cout, stride=stride,
+                                                                bottleneck=bottleneck, conv1_stride=conv1_stride))
+        self.features.add_module("post_activ", PreResActivation(in_channels=width))
+        self.finish(width)
 
 
 def get_preresnet(blocks, bottleneck=None, conv1_stride=True, width_scale=1.0, model_name=None, pretrained=False,
@@ -169,48 +154,24 @@ def get_preresnet(blocks, bottleneck=None, conv1_stride=True, width_scale=1.0, m
     """Depth table and channel plan of reference preresnet.py:320-369 (same table as ResNet plus 269)."""
     if bottleneck is None:
         bottleneck = (blocks >= 50)
-    if blocks == 269:
-        layers = [3, 30, 48, 8]
-    else:
-        layers = resnet_layers(blocks, bottleneck, what="PreResNet")
-    assert (sum(layers) * (3 if bottleneck else 2) + 2 == blocks)
-    init_block_channels = 64
-    channels_per_layers = [64, 128, 256, 512]
-    if bottleneck:
-        channels_per_layers = [ci * 4 for ci in channels_per_layers]
-    channels = [[ci] * li for (ci, li) in zip(channels_per_layers, layers)]
-    if width_scale != 1.0:
-        channels = [[int(cij * width_scale) if (i != len(channels) - 1) or (j != len(ci) - 1) else cij
-                     for j, cij in enumerate(ci)] for i, ci in enumerate(channels)]
-        init_block_channels = int(init_block_channels * width_scale)
-    net = PreResNet(channels=channels, init_block_channels=init_block_channels, bottleneck=bottleneck,
+    net = PreResNet(channels=resnet_channels(blocks, bottleneck, "PreResNet", RESNET_DEPTHS + (269,), width_scale),
+                    init_block_channels=(64 if width_scale == 1.0 else int(64 * width_scale)), bottleneck=bottleneck,
                     conv1_stride=conv1_stride, **kwargs)
     return maybe_load_pretrained(net, model_name, pretrained, root)
 
 
 # name -> get_preresnet arguments (reference preresnet.py:372-878)
-_VARIANTS = {
+_B = dict(conv1_stride=False)
+_BC = dict(bottleneck=True, conv1_stride=False)
+register_variants(__name__, get_preresnet, {
     "preresnet10": dict(blocks=10), "preresnet12": dict(blocks=12), "preresnet14": dict(blocks=14),
-    "preresnetbc14b": dict(blocks=14, bottleneck=True, conv1_stride=False), "preresnet16": dict(blocks=16),
+    "preresnetbc14b": dict(blocks=14, **_BC), "preresnet16": dict(blocks=16),
     "preresnet18_wd4": dict(blocks=18, width_scale=0.25), "preresnet18_wd2": dict(blocks=18, width_scale=0.5),
     "preresnet18_w3d4": dict(blocks=18, width_scale=0.75), "preresnet18": dict(blocks=18),
-    "preresnet26": dict(blocks=26, bottleneck=False), "preresnetbc26b": dict(blocks=26, bottleneck=True, conv1_stride=False),
-    "preresnet34": dict(blocks=34), "preresnetbc38b": dict(blocks=38, bottleneck=True, conv1_stride=False),
-    "preresnet50": dict(blocks=50), "preresnet50b": dict(blocks=50, conv1_stride=False),
-    "preresnet101": dict(blocks=101), "preresnet101b": dict(blocks=101, conv1_stride=False),
-    "preresnet152": dict(blocks=152), "preresnet152b": dict(blocks=152, conv1_stride=False),
-    "preresnet200": dict(blocks=200), "preresnet200b": dict(blocks=200, conv1_stride=False),
-    "preresnet269b": dict(blocks=269, conv1_stride=False),
-}
-
-
-def _variant(name, args):
-    def factory(**kwargs):
-        return get_preresnet(model_name=name, **dict(args, **kwargs))
-    factory.__name__ = name
-    factory.__doc__ = "PreResNet variant `{}` (reference preresnet.py:372-878).".format(name)
-    return factory
-
-
-for _name, _args in _VARIANTS.items():
-    globals()[_name] = _variant(_name, _args)
+    "preresnet26": dict(blocks=26, bottleneck=False), "preresnetbc26b": dict(blocks=26, **_BC),
+    "preresnet34": dict(blocks=34), "preresnetbc38b": dict(blocks=38, **_BC),
+    "preresnet50": dict(blocks=50), "preresnet50b": dict(blocks=50, **_B),
+    "preresnet101": dict(blocks=101), "preresnet101b": dict(blocks=101, **_B),
+    "preresnet152": dict(blocks=152), "preresnet152b": dict(blocks=152, **_B),
+    "preresnet200": dict(blocks=200), "preresnet200b": dict(blocks=200, **_B),
+    "preresnet269b": dict(blocks=269, **_B)})

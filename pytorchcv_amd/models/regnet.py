@@ -17,7 +17,9 @@ import numpy as np
 import torch.nn as nn
 from .common.conv import conv1x1_block, conv3x3_block
 from .common.att import SEBlock
-from ._tail import GlobalAvgPool2dNHWC, LinearHead, run_net, maybe_load_pretrained, init_conv_params, DEFAULT_ROOT
+from .resnet import SkipUnit
+from ._build import ClassifierNet, add_stages, register_variants, stage_table
+from ._tail import GlobalAvgPool2dNHWC, maybe_load_pretrained, DEFAULT_ROOT
 from .. import engine
 
 
@@ -45,51 +47,27 @@ class RegNetBottleneck(nn.Module):
         return engine.boundary(self, x, lambda a: self._run(a, residual, post_act))
 
 
-class RegNetUnit(nn.Module):
+class RegNetUnit(SkipUnit):
     """relu(body(x) + identity) (reference regnet.py:75-123); the identity a strided 1x1 block where the shape changes."""
     def __init__(self, in_channels, out_channels, stride, groups, use_se):
         super(RegNetUnit, self).__init__()
-        self.resize_identity = (in_channels != out_channels) or (stride != 1)
         self.body = RegNetBottleneck(in_channels=in_channels, out_channels=out_channels, stride=stride, groups=groups, use_se=use_se)
-        if self.resize_identity:
-            self.identity_conv = conv1x1_block(in_channels=in_channels, out_channels=out_channels, stride=stride, activation=None)
-        self.activ = nn.ReLU(inplace=True)
-
-    def run(self, a):
-        identity = self.identity_conv(a) if self.resize_identity else a
-        return self.body(a, residual=identity, post_act=self.activ)
-
-    def forward(self, x):
-        return engine.boundary(self, x, self.run)
+        self.add_skip(in_channels, out_channels, stride)
 
 
-class RegNet(nn.Module):
+class RegNet(ClassifierNet):
     """`features` (init_block, stage1..4 of unit1..n, final_pool) + `output` Linear (reference regnet.py:126-197)."""
     pcv_16bit = "fp16"      # the 16-bit mode "auto" resolves to for this family (engine.compute_dtype_of; DESIGN.md section 3)
 
     def __init__(self, channels, init_block_channels, groups, use_se, in_channels=3, in_size=(224, 224), num_classes=1000):
-        super(RegNet, self).__init__()
-        self.in_size = in_size
-        self.num_classes = num_classes
-        self.features = nn.Sequential()
+        super(RegNet, self).__init__(in_size, num_classes)
         self.features.add_module("init_block", conv3x3_block(in_channels=in_channels, out_channels=init_block_channels, stride=2,
                                                              padding=1))
-        in_channels = init_block_channels
-        for i, (channels_per_stage, groups_per_stage) in enumerate(zip(channels, groups)):
-            stage = nn.Sequential()
-            for j, out_channels in enumerate(channels_per_stage):
-                stride = 2 if (j == 0) else 1
-                stage.add_module("unit{}".format(j + 1), RegNetUnit(in_channels=in_channels, out_channels=out_channels, stride=stride,
-                                                                   groups=groups_per_stage, use_se=use_se))
-                in_channels = out_channels
-            self.features.add_module("stage{}".format(i + 1), stage)
-        self.features.add_module("final_pool", GlobalAvgPool2dNHWC(output_size=1, fp32_out=True))
-        self.output = LinearHead(in_features=in_channels, out_features=num_classes)
-        init_conv_params(self)
-        engine.stamp_family_dtype(self)                    # sub-modules called on their own resolve "auto" like the net
-
-    def forward(self, x):
-        return run_net(self, x, self.output)
+        width = add_stages(
+            self.features, init_block_channels, channels, downsample_first=True,
+            make_unit=lambda cin, cout, stride, i, j: RegNetUnit(in_channels=cin, out_channels=cout, stride=stride,
+                                                                 groups=groups[i], use_se=use_se))
+        self.finish(width, pool=GlobalAvgPool2dNHWC(output_size=1, fp32_out=True))
 
 
 def regnet_widths(channels_init, channels_slope, channels_mult, depth, groups):
@@ -110,8 +88,7 @@ def regnet_widths(channels_init, channels_slope, channels_mult, depth, groups):
 def get_regnet(channels_init, channels_slope, channels_mult, depth, groups, use_se=False, model_name=None, pretrained=False,
                root=DEFAULT_ROOT, **kwargs):
     channels_per_stage, layers, groups_per_stage = regnet_widths(channels_init, channels_slope, channels_mult, depth, groups)
-    channels = [[ci] * li for (ci, li) in zip(channels_per_stage, layers)]
-    net = RegNet(channels=channels, init_block_channels=32, groups=groups_per_stage, use_se=use_se, **kwargs)
+    net = RegNet(channels=stage_table(channels_per_stage, layers), init_block_channels=32, groups=groups_per_stage, use_se=use_se, **kwargs)
     return maybe_load_pretrained(net, model_name, pretrained, root)
 
 
@@ -126,16 +103,7 @@ _Y = {"002": (24, 36.44, 2.49, 13, 8), "004": (48, 27.89, 2.09, 16, 8), "006": (
       "320": (232, 115.89, 2.53, 20, 232)}
 
 
-def _factory(name, cfg, use_se):
-    def fn(**kwargs):
-        return get_regnet(channels_init=cfg[0], channels_slope=cfg[1], channels_mult=cfg[2], depth=cfg[3], groups=cfg[4],
-                          use_se=use_se, model_name=name, **kwargs)
-    fn.__name__ = name
-    fn.__doc__ = "RegNet{}-{} (reference regnet.py, `{}`).".format("Y" if use_se else "X", name[-3:], name)
-    return fn
-
-
-for _k, _cfg in _X.items():
-    globals()["regnetx" + _k] = _factory("regnetx" + _k, _cfg, False)
-for _k, _cfg in _Y.items():
-    globals()["regnety" + _k] = _factory("regnety" + _k, _cfg, True)
+_KEYS = ("channels_init", "channels_slope", "channels_mult", "depth", "groups")
+register_variants(__name__, get_regnet, dict(
+    [("regnetx" + k, dict(zip(_KEYS, cfg))) for k, cfg in _X.items()] +
+    [("regnety" + k, dict(zip(_KEYS, cfg), use_se=True)) for k, cfg in _Y.items()]))

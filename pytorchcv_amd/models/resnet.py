@@ -6,13 +6,14 @@
 
 __all__ = ['ResNet', 'resnet10', 'resnet12', 'resnet14', 'resnetbc14b', 'resnet16', 'resnet18', 'resnet26', 'resnetbc26b',
            'resnet34', 'resnetbc38b', 'resnet50', 'resnet50b', 'resnet101', 'resnet101b', 'resnet152', 'resnet152b',
-           'ResBlock', 'ResBottleneck', 'ResUnit', 'ResStage', 'ResInitBlock', 'get_resnet']
+           'ResBlock', 'ResBottleneck', 'SkipUnit', 'ResUnit', 'ResStage', 'ResInitBlock', 'get_resnet']
 
 import torch.nn as nn
 from .common.activ import lambda_relu
 from .common.norm import lambda_batchnorm2d
 from .common.conv import conv1x1_block, conv3x3_block, conv7x7_block, conv_block_pair, conv_block_maxpool, conv_block_bottleneck
-from ._tail import MaxPool2dNHWC, AvgPool2dNHWC, LinearHead, run_net, maybe_load_pretrained, init_conv_params, DEFAULT_ROOT
+from ._build import ClassifierNet, add_stages, register_variants, stage_table
+from ._tail import MaxPool2dNHWC, maybe_load_pretrained, DEFAULT_ROOT
 from .. import engine
 
 
@@ -49,13 +50,41 @@ class ResBottleneck(nn.Module):
         return engine.boundary(self, x, lambda a: self.conv3(self.conv2(self.conv1(a)), residual=residual, post_act=post_act))
 
 
-class ResUnit(nn.Module):
+class SkipUnit(nn.Module):
+    """Base of the residual units: owns `resize_identity`, the skip-path block `identity_conv` (present only where the unit
+    changes the shape), the activation `activ` behind the add, `_identity(a)` and the hot-path `forward`. A subclass registers
+    its children in the reference's order, which is the state_dict order: `body` and whatever the reference has in front of
+    the skip block (`se`), then `self.add_skip(...)`, then what it has behind it (`cbam`); it writes `_run(a)`."""
+    pcv_chainable = False        # True: ResStage hands `run_chained` the first convolution's output and fuses the last one forward
+
+    def add_skip(self, in_channels, out_channels, stride, block=conv1x1_block, activation=lambda_relu(), name="identity_conv",
+                 **block_args):
+        """`block(in_channels, out_channels, stride, **block_args)` as `name` where the shape changes, then `activ` (None: the
+        unit has none, or places it itself). The default block is the reference's 1x1 convolution + BN without activation."""
+        self.resize_identity = (in_channels != out_channels) or (stride != 1)
+        if self.resize_identity:
+            if block is conv1x1_block:
+                block_args["activation"] = None
+            self.add_module(name, block(in_channels=in_channels, out_channels=out_channels, stride=stride, **block_args))
+        if activation is not None:
+            self.activ = activation()
+
+    def _identity(self, a):
+        return self.identity_conv(a) if self.resize_identity else a
+
+    def _run(self, a):
+        return self.body(a, residual=self._identity(a), post_act=self.activ)
+
+    def forward(self, x):
+        return engine.boundary(self, x, self._run)
+
+
+class ResUnit(SkipUnit):
     """relu(body(x) + identity) (reference resnet.py:143-229)."""
     def __init__(self, in_channels, out_channels, stride=1, padding=1, dilation=1, bias=False,
                  normalization=lambda_batchnorm2d(), bottleneck=True, conv1_stride=False, activation=lambda_relu(),
                  final_body_activation=None, final_activation=lambda_relu()):
         super(ResUnit, self).__init__()
-        self.resize_identity = (in_channels != out_channels) or (stride != 1)
         if bottleneck:
             self.body = ResBottleneck(in_channels=in_channels, out_channels=out_channels, stride=stride, padding=padding,
                                       dilation=dilation, bias=bias, normalization=normalization, conv1_stride=conv1_stride,
@@ -63,14 +92,8 @@ class ResUnit(nn.Module):
         else:
             self.body = ResBlock(in_channels=in_channels, out_channels=out_channels, stride=stride, bias=bias,
                                  normalization=normalization, activation=activation, final_activation=final_body_activation)
-        if self.resize_identity:
-            self.identity_conv = conv1x1_block(in_channels=in_channels, out_channels=out_channels, stride=stride, bias=bias,
-                                               normalization=normalization, activation=None)
-        self.activ = final_activation()
-
-    def _run(self, a):
-        identity = self.identity_conv(a) if self.resize_identity else a
-        return self.body(a, residual=identity, post_act=self.activ)
+        self.add_skip(in_channels, out_channels, stride, activation=final_activation, bias=bias, normalization=normalization)
+        self.pcv_chainable = bool(bottleneck)        # ResStage chains the bottleneck units only
 
     def run_chained(self, a, conv1_out=None, next_unit=None):
         """Stage-level execution of a bottleneck unit: `conv1_out` is this unit's first convolution when the previous unit
@@ -90,7 +113,7 @@ class ResUnit(nn.Module):
             pair = conv_block_pair(body.conv3, y, None, self.activ, next_unit.body.conv1, id_block=self.identity_conv, x0=a)
             if pair is not None:
                 return pair
-        identity = self.identity_conv(a) if self.resize_identity else a
+        identity = self._identity(a)
         if next_unit is not None:
             pair = conv_block_pair(body.conv3, y, identity, self.activ, next_unit.body.conv1)
             if pair is not None:
@@ -109,9 +132,6 @@ class ResUnit(nn.Module):
         return conv_block_bottleneck(body.conv1, body.conv2, body.conv3, x, self.activ,
                                      id_block=self.identity_conv if self.resize_identity else None, probe=True)
 
-    def forward(self, x):
-        return engine.boundary(self, x, self._run)
-
 
 class ResStage(nn.Sequential):
     """A stage of units (plain nn.Sequential in the reference, resnet.py:297-313; same child names, same state_dict). On
@@ -119,7 +139,7 @@ class ResStage(nn.Sequential):
     first one can share a launch."""
     def forward(self, x):
         units = list(self.children())
-        chainable = all((isinstance(u, ResUnit) and isinstance(u.body, ResBottleneck)) or getattr(u, "pcv_chainable", False) for u in units)
+        chainable = all(getattr(u, "pcv_chainable", False) for u in units)
         if not isinstance(x, engine.NHWC) or not chainable:
             return super(ResStage, self).forward(x)
         conv1_out = None
@@ -139,131 +159,67 @@ class ResInitBlock(nn.Module):
         return engine.boundary(self, x, lambda a: conv_block_maxpool(self.conv, a, self.pool), stem=True)
 
 
-class ResNet(nn.Module):
+class ResNet(ClassifierNet):
     """`features` (init_block, stage1..4 of unit1..n, final_pool) + `output` Linear (reference resnet.py:266-337)."""
     def __init__(self, channels, init_block_channels, bottleneck, conv1_stride, in_channels=3, in_size=(224, 224),
                  num_classes=1000):
-        super(ResNet, self).__init__()
-        self.in_size = in_size
-        self.num_classes = num_classes
-        self.features = nn.Sequential()
+        super(ResNet, self).__init__(in_size, num_classes)
         self.features.add_module("init_block", ResInitBlock(in_channels=in_channels, out_channels=init_block_channels))
-        in_channels = init_block_channels
-        for i, channels_per_stage in enumerate(channels):
-            stage = ResStage()
-            for j, out_channels in enumerate(channels_per_stage):
-                stride = 2 if (j == 0) and (i != 0) else 1
-                stage.add_module("unit{}".format(j + 1), ResUnit(in_channels=in_channels, out_channels=out_channels,
-                                                                 stride=stride, bottleneck=bottleneck,
-                                                                 conv1_stride=conv1_stride))
-                in_channels = out_channels
-            self.features.add_module("stage{}".format(i + 1), stage)
-        self.features.add_module("final_pool", AvgPool2dNHWC(kernel_size=7, stride=1, fp32_out=True))
-        self.output = LinearHead(in_features=in_channels, out_features=num_classes)
-        init_conv_params(self)
-
-    def forward(self, x):
-        return run_net(self, x, self.output)
+        self.finish(add_stages(
+            self.features, init_block_channels, channels, container=ResStage,
+            make_unit=lambda cin, cout, stride, i, j: ResUnit(in_channels=cin, out_channels=cout, stride=stride,
+                                                              bottleneck=bottleneck, conv1_stride=conv1_stride)))
 
 
+# The one depth table of the ResNet-shaped families (reference resnet.py:373-411; 269 is PreResNet's / ResNeSt's). Depths 14, 26
+# and 38 depend on the block type, see resnet_layers.
 _LAYERS = {10: [1, 1, 1, 1], 12: [2, 1, 1, 1], 16: [2, 2, 2, 1], 18: [2, 2, 2, 2], 34: [3, 4, 6, 3], 50: [3, 4, 6, 3],
-           101: [3, 4, 23, 3], 152: [3, 8, 36, 3], 200: [3, 24, 36, 3]}
+           101: [3, 4, 23, 3], 152: [3, 8, 36, 3], 200: [3, 24, 36, 3], 269: [3, 30, 48, 8]}
+RESNET_DEPTHS = (10, 12, 14, 16, 18, 26, 34, 38, 50, 101, 152, 200)
 
 
-def resnet_layers(blocks, bottleneck, what="ResNet"):
-    """Units per stage for a depth (reference resnet.py:373-411)."""
-    if blocks == 14:
+def resnet_layers(blocks, bottleneck, what="ResNet", depths=RESNET_DEPTHS):
+    """Units per stage for a depth; `depths` are the ones the family `what` has (every reference table is a subset of this one)."""
+    if blocks not in depths:
+        layers = None
+    elif blocks == 14:
         layers = [1, 1, 1, 1] if bottleneck else [2, 2, 1, 1]
     elif blocks == 26:
         layers = [2, 2, 2, 2] if bottleneck else [3, 3, 3, 3]
-    elif blocks == 38 and bottleneck:
-        layers = [3, 3, 3, 3]
-    elif blocks in _LAYERS:
-        layers = _LAYERS[blocks]
+    elif blocks == 38:
+        layers = [3, 3, 3, 3] if bottleneck else None
     else:
+        layers = _LAYERS[blocks]
+    if layers is None:
         raise ValueError("Unsupported {} with number of blocks: {}".format(what, blocks))
     assert (sum(layers) * (3 if bottleneck else 2) + 2 == blocks)
     return layers
+
+
+def resnet_channels(blocks, bottleneck, what="ResNet", depths=RESNET_DEPTHS, width_scale=1.0):
+    """The stage table of a depth: 64 .. 512 channels (x4 with bottlenecks); `width_scale` spares the very last unit."""
+    table = stage_table([w * (4 if bottleneck else 1) for w in (64, 128, 256, 512)], resnet_layers(blocks, bottleneck, what, depths))
+    if width_scale != 1.0:
+        table = [[int(c * width_scale) for c in stage] for stage in table]
+        table[-1][-1] = 512 * (4 if bottleneck else 1)
+    return table
 
 
 def get_resnet(blocks, bottleneck=None, conv1_stride=True, width_scale=1.0, model_name=None, pretrained=False,
                root=DEFAULT_ROOT, **kwargs):
     if bottleneck is None:
         bottleneck = (blocks >= 50)
-    layers = resnet_layers(blocks, bottleneck)
-    init_block_channels = 64
-    widths = [64, 128, 256, 512]
-    if bottleneck:
-        widths = [w * 4 for w in widths]
-    channels = [[w] * n for (w, n) in zip(widths, layers)]
-    if width_scale != 1.0:
-        last = (len(channels) - 1, len(channels[-1]) - 1)
-        channels = [[int(c * width_scale) if (i, j) != last else c for j, c in enumerate(ci)] for i, ci in enumerate(channels)]
-        init_block_channels = int(init_block_channels * width_scale)
-    net = ResNet(channels=channels, init_block_channels=init_block_channels, bottleneck=bottleneck, conv1_stride=conv1_stride,
-                 **kwargs)
+    net = ResNet(channels=resnet_channels(blocks, bottleneck, width_scale=width_scale),
+                 init_block_channels=(64 if width_scale == 1.0 else int(64 * width_scale)), bottleneck=bottleneck,
+                 conv1_stride=conv1_stride, **kwargs)
     return maybe_load_pretrained(net, model_name, pretrained, root)
 
 
-def resnet10(**kwargs):
-    return get_resnet(blocks=10, model_name="resnet10", **kwargs)
-
-
-def resnet12(**kwargs):
-    return get_resnet(blocks=12, model_name="resnet12", **kwargs)
-
-
-def resnet14(**kwargs):
-    return get_resnet(blocks=14, model_name="resnet14", **kwargs)
-
-
-def resnetbc14b(**kwargs):
-    return get_resnet(blocks=14, bottleneck=True, conv1_stride=False, model_name="resnetbc14b", **kwargs)
-
-
-def resnet16(**kwargs):
-    return get_resnet(blocks=16, model_name="resnet16", **kwargs)
-
-
-def resnet18(**kwargs):
-    return get_resnet(blocks=18, model_name="resnet18", **kwargs)
-
-
-def resnet26(**kwargs):
-    return get_resnet(blocks=26, bottleneck=False, model_name="resnet26", **kwargs)
-
-
-def resnetbc26b(**kwargs):
-    return get_resnet(blocks=26, bottleneck=True, conv1_stride=False, model_name="resnetbc26b", **kwargs)
-
-
-def resnet34(**kwargs):
-    return get_resnet(blocks=34, model_name="resnet34", **kwargs)
-
-
-def resnetbc38b(**kwargs):
-    return get_resnet(blocks=38, bottleneck=True, conv1_stride=False, model_name="resnetbc38b", **kwargs)
-
-
-def resnet50(**kwargs):
-    return get_resnet(blocks=50, model_name="resnet50", **kwargs)
-
-
-def resnet50b(**kwargs):
-    return get_resnet(blocks=50, conv1_stride=False, model_name="resnet50b", **kwargs)
-
-
-def resnet101(**kwargs):
-    return get_resnet(blocks=101, model_name="resnet101", **kwargs)
-
-
-def resnet101b(**kwargs):
-    return get_resnet(blocks=101, conv1_stride=False, model_name="resnet101b", **kwargs)
-
-
-def resnet152(**kwargs):
-    return get_resnet(blocks=152, model_name="resnet152", **kwargs)
-
-
-def resnet152b(**kwargs):
-    return get_resnet(blocks=152, conv1_stride=False, model_name="resnet152b", **kwargs)
+_B = dict(conv1_stride=False)                    # the "b" nets: stride on the 3x3
+_BC = dict(bottleneck=True, conv1_stride=False)  # the "bc..b" nets: bottlenecks at a basic-block depth
+register_variants(__name__, get_resnet, {
+    "resnet10": dict(blocks=10), "resnet12": dict(blocks=12), "resnet14": dict(blocks=14), "resnetbc14b": dict(blocks=14, **_BC),
+    "resnet16": dict(blocks=16), "resnet18": dict(blocks=18), "resnet26": dict(blocks=26, bottleneck=False),
+    "resnetbc26b": dict(blocks=26, **_BC), "resnet34": dict(blocks=34), "resnetbc38b": dict(blocks=38, **_BC),
+    "resnet50": dict(blocks=50), "resnet50b": dict(blocks=50, **_B), "resnet101": dict(blocks=101),
+    "resnet101b": dict(blocks=101, **_B), "resnet152": dict(blocks=152), "resnet152b": dict(blocks=152, **_B)})

@@ -8,8 +8,8 @@ __all__ = ['ResNeXt', 'ResNeXtBottleneck', 'ResNeXtUnit', 'get_resnext']
 import math
 import torch.nn as nn
 from .common.conv import conv1x1_block, conv3x3_block, conv_block_pair
-from .resnet import ResInitBlock, ResStage
-from ._build import ClassifierNet, add_stages, register_variants, stage_table
+from .resnet import SkipUnit, ResInitBlock, ResStage, resnet_channels
+from ._build import ClassifierNet, add_stages, register_variants
 from ._tail import maybe_load_pretrained, DEFAULT_ROOT
 from .. import engine
 
@@ -28,27 +28,19 @@ class ResNeXtBottleneck(nn.Module):
         return engine.boundary(self, x, lambda a: self.conv3(self.conv2(self.conv1(a)), residual=residual, post_act=post_act))
 
 
-class ResNeXtUnit(nn.Module):
+class ResNeXtUnit(SkipUnit):
     def __init__(self, in_channels, out_channels, stride, cardinality, bottleneck_width):
         super(ResNeXtUnit, self).__init__()
-        self.resize_identity = (in_channels != out_channels) or (stride != 1)
         self.body = ResNeXtBottleneck(in_channels=in_channels, out_channels=out_channels, stride=stride,
                                       cardinality=cardinality, bottleneck_width=bottleneck_width)
-        if self.resize_identity:
-            self.identity_conv = conv1x1_block(in_channels=in_channels, out_channels=out_channels, stride=stride,
-                                               activation=None)
-        self.activ = nn.ReLU(inplace=True)
+        self.add_skip(in_channels, out_channels, stride)
 
     pcv_chainable = True         # ResStage may hand this unit its first convolution's output and fuse its last one forward
-
-    def _run(self, a):
-        identity = self.identity_conv(a) if self.resize_identity else a
-        return self.body(a, residual=identity, post_act=self.activ)
 
     def run_chained(self, a, conv1_out=None, next_unit=None):
         """As ResUnit.run_chained: the unit's last 1x1 (+ skip add + ReLU) and the next unit's first 1x1 as one launch when the
         pair is covered (128 -> 256 -> 128 and 256 -> 512 -> 256 in the 32x4d nets)."""
-        identity = self.identity_conv(a) if self.resize_identity else a
+        identity = self._identity(a)
         body = self.body
         y = body.conv2(conv1_out if conv1_out is not None else body.conv1(a))
         if next_unit is not None:
@@ -57,29 +49,20 @@ class ResNeXtUnit(nn.Module):
                 return pair
         return body.conv3(y, residual=identity, post_act=self.activ), None
 
-    def forward(self, x):
-        return engine.boundary(self, x, self._run)
-
 
 class ResNeXt(ClassifierNet):
     def __init__(self, channels, init_block_channels, cardinality, bottleneck_width, in_channels=3, in_size=(224, 224),
                  num_classes=1000):
         super(ResNeXt, self).__init__(in_size, num_classes)
         self.features.add_module("init_block", ResInitBlock(in_channels=in_channels, out_channels=init_block_channels))
-        width = add_stages(
+        self.finish(add_stages(
             self.features, init_block_channels, channels, container=ResStage,
             make_unit=lambda cin, cout, stride, i, j: ResNeXtUnit(in_channels=cin, out_channels=cout, stride=stride,
-                                                                  cardinality=cardinality, bottleneck_width=bottleneck_width))
-        self.finish(width)
-
-
-_DEPTHS = {14: (1, 1, 1, 1), 26: (2, 2, 2, 2), 38: (3, 3, 3, 3), 50: (3, 4, 6, 3), 101: (3, 4, 23, 3)}     # bottleneck units per stage
+                                                                  cardinality=cardinality, bottleneck_width=bottleneck_width)))
 
 
 def get_resnext(blocks, cardinality, bottleneck_width, model_name=None, pretrained=False, root=DEFAULT_ROOT, **kwargs):
-    if blocks not in _DEPTHS:
-        raise ValueError("Unsupported ResNeXt with number of blocks: {}".format(blocks))
-    net = ResNeXt(channels=stage_table((256, 512, 1024, 2048), _DEPTHS[blocks]), init_block_channels=64,
+    net = ResNeXt(channels=resnet_channels(blocks, True, what="ResNeXt", depths=(14, 26, 38, 50, 101)), init_block_channels=64,
                   cardinality=cardinality, bottleneck_width=bottleneck_width, **kwargs)
     return maybe_load_pretrained(net, model_name, pretrained, root)
 

@@ -12,7 +12,8 @@ __all__ = ['ShuffleNetV2', 'shufflenetv2_wd2', 'shufflenetv2_w1', 'shufflenetv2_
 import torch.nn as nn
 from .common.conv import conv1x1, depthwise_conv3x3, conv1x1_block, conv3x3_block
 from .common.att import SEBlock
-from ._tail import MaxPool2dNHWC, AvgPool2dNHWC, LinearHead, run_net, maybe_load_pretrained, init_conv_params, DEFAULT_ROOT
+from ._build import ClassifierNet, add_stages, register_variants, scale_widths, stage_table
+from ._tail import MaxPool2dNHWC, maybe_load_pretrained, DEFAULT_ROOT
 from .. import engine
 
 
@@ -99,59 +100,29 @@ class ShuffleInitBlock(nn.Module):
         return engine.boundary(self, x, lambda a: self.pool(self.conv(a)), stem=True)
 
 
-class ShuffleNetV2(nn.Module):
+class ShuffleNetV2(ClassifierNet):
     def __init__(self, channels, init_block_channels, final_block_channels, use_se=False, use_residual=False, in_channels=3,
                  in_size=(224, 224), num_classes=1000):
-        super(ShuffleNetV2, self).__init__()
-        self.in_size = in_size
-        self.num_classes = num_classes
-        self.features = nn.Sequential()
+        super(ShuffleNetV2, self).__init__(in_size, num_classes)
         self.features.add_module("init_block", ShuffleInitBlock(in_channels=in_channels, out_channels=init_block_channels))
-        in_channels = init_block_channels
-        for i, channels_per_stage in enumerate(channels):
-            stage = nn.Sequential()
-            for j, out_channels in enumerate(channels_per_stage):
-                stage.add_module("unit{}".format(j + 1), ShuffleUnit(in_channels=in_channels, out_channels=out_channels,
-                                                                    downsample=(j == 0), use_se=use_se,
-                                                                    use_residual=use_residual))
-                in_channels = out_channels
-            self.features.add_module("stage{}".format(i + 1), stage)
-        self.features.add_module("final_block", conv1x1_block(in_channels=in_channels, out_channels=final_block_channels))
-        in_channels = final_block_channels
-        self.features.add_module("final_pool", AvgPool2dNHWC(kernel_size=7, stride=1, fp32_out=True))
-        self.output = LinearHead(in_features=in_channels, out_features=num_classes)
-        init_conv_params(self)
-
-    def forward(self, x):
-        return run_net(self, x, self.output)
+        width = add_stages(
+            self.features, init_block_channels, channels, downsample_first=True,
+            make_unit=lambda cin, cout, stride, i, j: ShuffleUnit(in_channels=cin, out_channels=cout, downsample=(stride == 2),
+                                                                  use_se=use_se, use_residual=use_residual))
+        self.features.add_module("final_block", conv1x1_block(in_channels=width, out_channels=final_block_channels))
+        self.finish(final_block_channels)
 
 
 def get_shufflenetv2(width_scale, model_name=None, pretrained=False, root=DEFAULT_ROOT, **kwargs):
     init_block_channels = 24
     final_block_channels = 1024
-    layers = [4, 8, 4]
-    channels_per_layers = [116, 232, 464]
-    channels = [[ci] * li for (ci, li) in zip(channels_per_layers, layers)]
-    if width_scale != 1.0:
-        channels = [[int(cij * width_scale) for cij in ci] for ci in channels]
-        if width_scale > 1.5:
-            final_block_channels = int(final_block_channels * width_scale)
-    net = ShuffleNetV2(channels=channels, init_block_channels=init_block_channels, final_block_channels=final_block_channels,
+    if width_scale > 1.5:
+        final_block_channels = int(final_block_channels * width_scale)
+    net = ShuffleNetV2(channels=scale_widths(stage_table([116, 232, 464], [4, 8, 4]), width_scale), init_block_channels=init_block_channels, final_block_channels=final_block_channels,
                        **kwargs)
     return maybe_load_pretrained(net, model_name, pretrained, root)
 
 
-def shufflenetv2_wd2(**kwargs):
-    return get_shufflenetv2(width_scale=(12.0 / 29.0), model_name="shufflenetv2_wd2", **kwargs)
-
-
-def shufflenetv2_w1(**kwargs):
-    return get_shufflenetv2(width_scale=1.0, model_name="shufflenetv2_w1", **kwargs)
-
-
-def shufflenetv2_w3d2(**kwargs):
-    return get_shufflenetv2(width_scale=(44.0 / 29.0), model_name="shufflenetv2_w3d2", **kwargs)
-
-
-def shufflenetv2_w2(**kwargs):
-    return get_shufflenetv2(width_scale=(61.0 / 29.0), model_name="shufflenetv2_w2", **kwargs)
+register_variants(__name__, get_shufflenetv2, {
+    "shufflenetv2_wd2": dict(width_scale=(12.0 / 29.0)), "shufflenetv2_w1": dict(width_scale=1.0),
+    "shufflenetv2_w3d2": dict(width_scale=(44.0 / 29.0)), "shufflenetv2_w2": dict(width_scale=(61.0 / 29.0))})

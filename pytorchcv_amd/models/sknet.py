@@ -11,8 +11,9 @@ import torch
 import torch.nn as nn
 from .common.conv import conv1x1, conv1x1_block, conv3x3_block
 from .common.att import fold_bn_into_fc, _FoldedMlp
-from .resnet import ResInitBlock
-from ._tail import AvgPool2dNHWC, LinearHead, run_net, maybe_load_pretrained, init_conv_params, DEFAULT_ROOT
+from .resnet import SkipUnit, ResInitBlock, resnet_channels
+from ._build import ClassifierNet, add_stages, register_variants
+from ._tail import maybe_load_pretrained, DEFAULT_ROOT
 from .. import engine
 
 
@@ -77,66 +78,28 @@ class SKNetBottleneck(nn.Module):
         return engine.boundary(self, x, lambda a: self.conv3(self.conv2(self.conv1(a)), residual=residual, post_act=post_act))
 
 
-class SKNetUnit(nn.Module):
+class SKNetUnit(SkipUnit):
     """relu(body(x) + identity) (reference sknet.py:133-176)."""
     def __init__(self, in_channels, out_channels, stride):
         super(SKNetUnit, self).__init__()
-        self.resize_identity = (in_channels != out_channels) or (stride != 1)
         self.body = SKNetBottleneck(in_channels=in_channels, out_channels=out_channels, stride=stride)
-        if self.resize_identity:
-            self.identity_conv = conv1x1_block(in_channels=in_channels, out_channels=out_channels, stride=stride, activation=None)
-        self.activ = nn.ReLU(inplace=True)
-
-    def _run(self, a):
-        identity = self.identity_conv(a) if self.resize_identity else a
-        return self.body(a, residual=identity, post_act=self.activ)
-
-    def forward(self, x):
-        return engine.boundary(self, x, self._run)
+        self.add_skip(in_channels, out_channels, stride)
 
 
-class SKNet(nn.Module):
+class SKNet(ClassifierNet):
     """`features` (ResInitBlock, stage1..4, final_pool) + `output` Linear (reference sknet.py:179-245)."""
     pcv_16bit = "fp16"      # the 16-bit mode "auto" resolves to for this family (engine.compute_dtype_of; DESIGN.md section 5.3d)
-    def __init__(self, channels, init_block_channels, in_channels=3, in_size=(224, 224), num_classes=1000):
-        super(SKNet, self).__init__()
-        self.in_size = in_size
-        self.num_classes = num_classes
-        self.features = nn.Sequential()
-        self.features.add_module("init_block", ResInitBlock(in_channels=in_channels, out_channels=init_block_channels))
-        in_channels = init_block_channels
-        for i, channels_per_stage in enumerate(channels):
-            stage = nn.Sequential()
-            for j, out_channels in enumerate(channels_per_stage):
-                stride = 2 if (j == 0) and (i != 0) else 1
-                stage.add_module("unit{}".format(j + 1), SKNetUnit(in_channels=in_channels, out_channels=out_channels, stride=stride))
-                in_channels = out_channels
-            self.features.add_module("stage{}".format(i + 1), stage)
-        self.features.add_module("final_pool", AvgPool2dNHWC(kernel_size=7, stride=1, fp32_out=True))
-        self.output = LinearHead(in_features=in_channels, out_features=num_classes)
-        init_conv_params(self)
-        engine.stamp_family_dtype(self)                    # sub-modules called on their own resolve "auto" like the net
 
-    def forward(self, x):
-        return run_net(self, x, self.output)
+    def __init__(self, channels, init_block_channels, in_channels=3, in_size=(224, 224), num_classes=1000):
+        super(SKNet, self).__init__(in_size, num_classes)
+        self.features.add_module("init_block", ResInitBlock(in_channels=in_channels, out_channels=init_block_channels))
+        self.finish(add_stages(self.features, init_block_channels, channels,
+                               make_unit=lambda cin, cout, stride, i, j: SKNetUnit(in_channels=cin, out_channels=cout, stride=stride)))
 
 
 def get_sknet(blocks, model_name=None, pretrained=False, root=DEFAULT_ROOT, **kwargs):
-    layers = {50: [3, 4, 6, 3], 101: [3, 4, 23, 3], 152: [3, 8, 36, 3]}.get(blocks)
-    if layers is None:
-        raise ValueError("Unsupported SKNet with number of blocks: {}".format(blocks))
-    channels = [[ci] * li for (ci, li) in zip([256, 512, 1024, 2048], layers)]
-    net = SKNet(channels=channels, init_block_channels=64, **kwargs)
+    net = SKNet(channels=resnet_channels(blocks, True, what="SKNet", depths=(50, 101, 152)), init_block_channels=64, **kwargs)
     return maybe_load_pretrained(net, model_name, pretrained, root)
 
 
-def sknet50(**kwargs):
-    return get_sknet(blocks=50, model_name="sknet50", **kwargs)
-
-
-def sknet101(**kwargs):
-    return get_sknet(blocks=101, model_name="sknet101", **kwargs)
-
-
-def sknet152(**kwargs):
-    return get_sknet(blocks=152, model_name="sknet152", **kwargs)
+register_variants(__name__, get_sknet, {"sknet{}".format(n): dict(blocks=n) for n in (50, 101, 152)})

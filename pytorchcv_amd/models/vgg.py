@@ -2,7 +2,9 @@
     VGG / BN-VGG for ImageNet-1K on the MI355X hot path (reference pytorchcv/models/vgg.py:17-330): 3x3 convolutions with
     bias (+ BN) + ReLU as single fused launches, 2x2 max pools, and the three dense layers of the classifier. The reference
     flattens the 512x7x7 map in NCHW order before `fc1`; on the NHWC path `fc1` is the same weight matrix viewed as a 7x7
-    valid convolution [4096, 512, 7, 7], so the flatten never materialises and the state_dict layout is unchanged.
+    valid convolution [4096, 512, 7, 7], so the flatten never materialises and the state_dict layout is unchanged. The net keeps
+    its own trunk loop and forward (not `add_stages` / `finish`): no init block, a `pool{i}` closing every stage, no `final_pool`,
+    a dense classifier, and a stride-1 first convolution (`stem=False`).
 """
 
 __all__ = ['VGG', 'get_vgg', 'vgg11', 'vgg13', 'vgg16', 'vgg19', 'bn_vgg11', 'bn_vgg13', 'bn_vgg16', 'bn_vgg19', 'bn_vgg11b',
@@ -12,6 +14,7 @@ import torch.nn as nn
 from .. import engine
 from .common.norm import lambda_batchnorm2d
 from .common.conv import conv3x3_block
+from ._build import ClassifierNet, register_variants, stage_table
 from ._tail import MaxPool2dNHWC, run_net, maybe_load_pretrained, init_conv_params, DEFAULT_ROOT
 
 
@@ -71,13 +74,10 @@ class VGGOutputBlock(nn.Module):
         return y.t.view(y.N, -1)[:, :self.fc3.out_features]
 
 
-class VGG(nn.Module):
+class VGG(ClassifierNet):
     def __init__(self, channels, bias=True, use_bn=False, in_channels=3, in_size=(224, 224), num_classes=1000):
-        super(VGG, self).__init__()
-        self.in_size = in_size
-        self.num_classes = num_classes
+        super(VGG, self).__init__(in_size, num_classes)
         normalization = lambda_batchnorm2d() if use_bn else None
-        self.features = nn.Sequential()
         for i, channels_per_stage in enumerate(channels):
             stage = nn.Sequential()
             for j, out_channels in enumerate(channels_per_stage):
@@ -98,54 +98,15 @@ def get_vgg(blocks, bias=True, use_bn=False, model_name=None, pretrained=False, 
     layers = {11: [1, 1, 2, 2, 2], 13: [2, 2, 2, 2, 2], 16: [2, 2, 3, 3, 3], 19: [2, 2, 4, 4, 4]}.get(blocks)
     if layers is None:
         raise ValueError("Unsupported VGG with number of blocks: {}".format(blocks))
-    channels = [[ci] * li for (ci, li) in zip([64, 128, 256, 512, 512], layers)]
-    net = VGG(channels=channels, bias=bias, use_bn=use_bn, **kwargs)
+    net = VGG(channels=stage_table([64, 128, 256, 512, 512], layers), bias=bias, use_bn=use_bn, **kwargs)
     return maybe_load_pretrained(net, model_name, pretrained, root)
 
 
-def vgg11(**kwargs):
-    return get_vgg(blocks=11, model_name="vgg11", **kwargs)
+def _variants():
+    """`vggN` (bias, no BN), `bn_vggN` (BN, no bias), `bn_vggNb` (both) (reference vgg.py:160-330)."""
+    for prefix, suffix, args in (("vgg", "", {}), ("bn_vgg", "", dict(bias=False, use_bn=True)), ("bn_vgg", "b", dict(bias=True, use_bn=True))):
+        for blocks in (11, 13, 16, 19):
+            yield "{}{}{}".format(prefix, blocks, suffix), dict(blocks=blocks, **args)
 
 
-def vgg13(**kwargs):
-    return get_vgg(blocks=13, model_name="vgg13", **kwargs)
-
-
-def vgg16(**kwargs):
-    return get_vgg(blocks=16, model_name="vgg16", **kwargs)
-
-
-def vgg19(**kwargs):
-    return get_vgg(blocks=19, model_name="vgg19", **kwargs)
-
-
-def bn_vgg11(**kwargs):
-    return get_vgg(blocks=11, bias=False, use_bn=True, model_name="bn_vgg11", **kwargs)
-
-
-def bn_vgg13(**kwargs):
-    return get_vgg(blocks=13, bias=False, use_bn=True, model_name="bn_vgg13", **kwargs)
-
-
-def bn_vgg16(**kwargs):
-    return get_vgg(blocks=16, bias=False, use_bn=True, model_name="bn_vgg16", **kwargs)
-
-
-def bn_vgg19(**kwargs):
-    return get_vgg(blocks=19, bias=False, use_bn=True, model_name="bn_vgg19", **kwargs)
-
-
-def bn_vgg11b(**kwargs):
-    return get_vgg(blocks=11, bias=True, use_bn=True, model_name="bn_vgg11b", **kwargs)
-
-
-def bn_vgg13b(**kwargs):
-    return get_vgg(blocks=13, bias=True, use_bn=True, model_name="bn_vgg13b", **kwargs)
-
-
-def bn_vgg16b(**kwargs):
-    return get_vgg(blocks=16, bias=True, use_bn=True, model_name="bn_vgg16b", **kwargs)
-
-
-def bn_vgg19b(**kwargs):
-    return get_vgg(blocks=19, bias=True, use_bn=True, model_name="bn_vgg19b", **kwargs)
+register_variants(__name__, get_vgg, dict(_variants()))

@@ -6,7 +6,7 @@
 
 __all__ = ['NHWC', 'DTYPES', 'default_dtype', 'set_compute_dtype', 'compute_dtype_of', 'Fp16Guard', 'fp16_overflow_count', 'from_nchw', 'to_nchw', 'ConvRunner',
            'MixConvRunner', 'ghost_dw', 'BnActRunner', 'IBNConvRunner', 'InstNormRunner', 'maxpool2d', 'avgpool2d', 'avgpool2d_pad', 'global_avgpool', 'se_excite', 'se_scale', 'se_forward', 'splat_forward', 'cbam_channel_gate', 'cbam_spatial', 'cbam_forward', 'channel_slice', 'cat_shuffle2', 'act_code',
-           'boundary', 'round8', 'channel_concat_into', 'interpolate', 'add', 'hr_fuse', 'hr_fuse_supported', 'classify']
+           'boundary', 'round8', 'source_key', 'channel_concat_into', 'interpolate', 'add', 'hr_fuse', 'hr_fuse_supported', 'classify']
 
 import os
 import ctypes
@@ -95,6 +95,10 @@ def round8(c: int) -> int:
     return (int(c) + 7) // 8 * 8
 
 
+def _even(w: int) -> int:
+    return (int(w) + 1) // 2 * 2
+
+
 class NHWC(object):
     """
     An activation on the hot path: `t` is a contiguous device tensor [N, H, wpitch, cpitch]; (H, W, C) is the logical
@@ -127,15 +131,15 @@ class NHWC(object):
         return s if dim is None else s[dim]
 
 
-class _ShapeOnly(object):
-    """What ConvRunner.desc reads of its input, for a tensor that does not exist yet."""
-    __slots__ = ("N", "H", "W", "C", "dtype", "wpitch", "cpitch")
+class ShapeOnly(object):
+    """A dense handle's shape, dtype and (optionally) device for a tensor that does not exist: what `ConvRunner.desc` and `prepare`
+    read of their input. The intermediate maps of a fused unit; a model asks with one whether a unit WOULD be covered before its
+    input exists (bottleneck_fused's probe)."""
+    __slots__ = ("N", "H", "W", "C", "dtype", "wpitch", "cpitch", "device")
+    dense = True
 
-    def __init__(self, N, H, W, C, dtype):
-        self.N, self.H, self.W, self.C, self.dtype, self.wpitch, self.cpitch = N, H, W, C, dtype, W, round8(C)
-
-
-ShapeOnly = _ShapeOnly      # (public name: a model asks whether a unit WOULD be covered before its input exists - bottleneck_fused's probe)
+    def __init__(self, N, H, W, C, dtype, device=None):
+        self.N, self.H, self.W, self.C, self.dtype, self.wpitch, self.cpitch, self.device = N, H, W, C, dtype, W, round8(C), device
 
 
 def _device_index(device) -> int:
@@ -172,6 +176,95 @@ def _call(device, name, *args, accept=()):
     return rc
 
 
+def _ptrs(r):
+    """(packed, scale, shift) pointers of a prepared runner; three Nones for no runner."""
+    return (_ptr(r.packed), _ptr(r.scale), _ptr(r.shift)) if r is not None else (None, None, None)
+
+
+def _check_residual(residual, shape, dtype, detail=False):
+    """A skip tensor (None passes) is a dense handle of exactly the output's physical shape and type."""
+    if residual is not None and (not residual.dense or residual.dtype != dtype or tuple(residual.t.shape) != shape):
+        raise RuntimeError("residual shape/dtype mismatch" + (": {} vs {}".format(tuple(residual.t.shape), shape) if detail else ""))
+
+
+def _split_batch(N: int, launch, n0: int = 0):
+    """Images [n0, n0 + N) through `launch(n0, n1, accept) -> rc`, which hands `accept` to `_call`: one launch addresses less than
+    2 GiB, so a range of more than one image may be refused as too large and is then halved, left half first. A single image is
+    launched with nothing accepted: any refusal raises in `_call`."""
+    n1 = n0 + N
+    accept = (_lib.PCV_ERR_TOO_LARGE,) if N > 1 else ()
+    if launch(n0, n1, accept) in accept:
+        mid = (n0 + n1) // 2
+        _split_batch(mid - n0, launch, n0)
+        _split_batch(n1 - mid, launch, mid)
+
+
+def source_key(tensors):
+    """Cache key over source tensors (None entries allowed): storage and version, so load_state_dict, .to() and in-place edits change it."""
+    return tuple([(t.data_ptr(), t._version) if t is not None else None for t in tensors])
+
+
+def _bn_fold_sources(bn, C: int, bias=None, what="into the conv epilogue"):
+    """The fp32 inputs of pcv_bn_fold over `C` physical channels, pure torch: (gamma, beta, mean, var, bias) of the eval-mode
+    BatchNorm2d `bn` (gamma 1, beta 0 without affine parameters) and the convolution's `bias`, each padded to C - gamma, beta, mean
+    and bias with 0, var with 1, so that a pad channel gets scale 0 and shift 0. `bn` None: four Nones (scale 1, shift bias)."""
+    def padded(t, fill=0.0):
+        t = t.detach().float()
+        return (F.pad(t, (0, C - t.numel()), value=fill) if t.numel() != C else t).contiguous()
+    bias = padded(bias) if bias is not None else None
+    if bn is None:
+        return None, None, None, None, bias
+    if not isinstance(bn, nn.BatchNorm2d):
+        raise NotImplementedError("only BatchNorm2d folds {}, got {}".format(what, type(bn).__name__))
+    mean = bn.running_mean
+    return (padded(bn.weight if bn.weight is not None else torch.ones_like(mean)),
+            padded(bn.bias if bn.bias is not None else torch.zeros_like(mean)), padded(mean), padded(bn.running_var, 1.0), bias)
+
+
+def _fold_bn(dev, bn, C: int, bias=None, what="into the conv epilogue"):
+    """(scale, shift): fp32 [C] on `dev` with y = scale * conv + shift = bn(conv + bias) (pcv_bn_fold). The sources it reads are
+    temporaries: the caller synchronises the stream once per prepare()."""
+    scale = torch.empty(C, dtype=torch.float32, device=dev)
+    shift = torch.empty(C, dtype=torch.float32, device=dev)
+    g, b, m, v, bias = _bn_fold_sources(bn, C, bias, what)
+    _call(dev, "bn_fold", C, _ptr(g), _ptr(b), _ptr(m), _ptr(v), ctypes.c_float(bn.eps if bn is not None else 0.0), _ptr(bias),
+          _ptr(scale), _ptr(shift))
+    return scale, shift
+
+
+class _DerivedState(object):
+    """What the runners that cache state folded from a module's parameters share: the key the state was built for, and whether the
+    state was RECEIVED (parallel.broadcast_packed_state) - then the local fp32 sources are not what it was derived from and nothing
+    may be re-derived from them. A subclass names its source tensors (`_sources`) and its refusal text (`_refusal`)."""
+    _refusal = None
+
+    def __init__(self):
+        self._key = None
+        self._foreign = False
+        self.packed = self.scale = self.shift = None
+
+    def _sources(self):
+        raise NotImplementedError
+
+    def _rebuilding(self):
+        """What prepare() calls once its key differs from `_key` (the same key returns before, inline: it is the per-forward path).
+        Received state is never rebuilt: a new key would re-derive it from THIS rank's fp32 tensors, which
+        broadcast_packed_state never updated - wrong logits with no error - so that raises; the caller re-synchronises the fp32
+        state first."""
+        if self._foreign:
+            raise RuntimeError(self._refusal)
+
+    def adopt_foreign_state(self):
+        """Called after the state was overwritten with another rank's (parallel.broadcast_packed_state): the cache key stays valid
+        for exactly the configuration it was built for, anything else raises in prepare()."""
+        self._foreign = True
+
+    def local_state_restored(self):
+        """The fp32 sources are authoritative again (parallel.broadcast_module_state, load_state_dict): re-derive on next use."""
+        self._foreign = False
+        self._key = None
+
+
 def _conv_out(d: ConvDesc, H: int, W: int):
     """(Ho, Wo) of the convolution `d` on an H x W map."""
     return ((H + d.pad_t + d.pad_b - d.dil_h * (d.kh - 1) - 1) // d.stride_h + 1,
@@ -195,7 +288,7 @@ class LazyNCHW(NHWC):
         N, C, H, W = x.shape
         self.src, self._conv, self._dtype_name = x, None, dtype
         self.N, self.H, self.W, self.C = N, H, W, C
-        self.wpitch, self.cpitch = (W + 1) // 2 * 2, 4
+        self.wpitch, self.cpitch = _even(W), 4
 
     @property
     def t(self):
@@ -218,11 +311,9 @@ class LazyNCHW(NHWC):
 
 def network_input(x: torch.Tensor, dtype: str) -> NHWC:
     """Handle of a net's fp32 NCHW input: lazy (the stem kernel reads the planes directly) when the stem layout applies."""
-    if x.dim() != 4:
-        raise ValueError("expected a 4-D NCHW tensor")
-    if x.shape[1] <= 3 and x.shape[3] % 4 == 0 and STEM_FROM_NCHW:
+    if x.dim() == 4 and x.shape[1] <= 3 and x.shape[3] % 4 == 0 and STEM_FROM_NCHW:
         return LazyNCHW(x.contiguous().float(), dtype)
-    return from_nchw(x, dtype, stem=True)
+    return from_nchw(x, dtype, stem=True)       # (which refuses anything but 4-D)
 
 
 def from_nchw(x: torch.Tensor, dtype: str, stem: bool = True) -> NHWC:
@@ -232,10 +323,7 @@ def from_nchw(x: torch.Tensor, dtype: str, stem: bool = True) -> NHWC:
     x = x.contiguous().float()
     N, C, H, W = x.shape
     code, tdt = DTYPES[dtype]
-    if C <= 4 and stem:
-        cp, wp = 4, (W + 1) // 2 * 2
-    else:
-        cp, wp = (C + 7) // 8 * 8, W
+    cp, wp = (4, _even(W)) if C <= 4 and stem else (round8(C), W)
     y = torch.empty((N, H, wp, cp), dtype=tdt, device=x.device)
     _call(x.device, "nchw_to_nhwc", _ptr(x), _ptr(y), N, C, H, W, cp, wp, code)
     return NHWC(y, N, H, W, C, wpitch=wp, cpitch=cp)
@@ -293,17 +381,22 @@ def _pair(v):
     return (int(v[0]), int(v[1])) if isinstance(v, (tuple, list)) else (int(v), int(v))
 
 
-class ConvRunner(object):
+class ConvRunner(_DerivedState):
     """
     Packed state of one Conv2d (+ optional BatchNorm2d) for one (device, dtype, input channel pitch): weights in the
     kernel's layout and the folded fp32 scale/shift. Rebuilt whenever a source parameter changes (load_state_dict, .to()).
     """
+    _refusal = ("this convolution's packed weights were received by parallel.broadcast_packed_state and would have to be re-packed "
+                "(the input's dtype / channel pitch / padding parity or a parameter changed), but this rank's fp32 parameters are "
+                "not the source's. Call parallel.broadcast_module_state(net) (or load_state_dict on every rank) before running "
+                "another configuration.")
+
     def __init__(self, conv: nn.Conv2d, bn, pad4=None):
+        super(ConvRunner, self).__init__()
         self.conv, self.bn, self.pad4 = conv, bn, pad4
-        self._key = None
-        self._foreign = False       # packed / scale / shift were RECEIVED (parallel.broadcast_packed_state): the local fp32 sources
-                                    # are not what they were derived from, so nothing may be re-derived from them
-        self.packed = self.scale = self.shift = None
+        self._sq_key = None                                                 # squeezed_excite's folded SE layers and their key
+        self._sq_w1 = self._sq_b1 = self._sq_w2 = self._sq_b2 = None
+        self._bnu_refused = set()                                           # bottleneck_fused: shapes the library refused (on conv1's runner)
         self.depthwise = (conv.groups > 1 and conv.groups == conv.in_channels == conv.out_channels)
         if 1 < conv.groups and not self.depthwise and (conv.in_channels % 8 or conv.out_channels % 8):
             raise NotImplementedError("grouped convolution with channel counts that are not multiples of 8")
@@ -328,8 +421,7 @@ class ConvRunner(object):
         # everything the packed blob and the scale/shift arrays depend on besides the source tensors: physical channel counts
         # (the fp32 classifier output keeps its logical width), output type, and the parity of the left padding (the stem
         # packing depends on it; TF-"same" mode changes it per call)
-        return (dtype, cpitch, d.Cin, d.Cout, d.groups, d.out_dtype, d.pad_l & 1) + \
-            tuple((t.data_ptr(), t._version) if t is not None else None for t in self._sources())
+        return (dtype, cpitch, d.Cin, d.Cout, d.groups, d.out_dtype, d.pad_l & 1) + source_key(self._sources())
 
     def desc(self, x: NHWC, act, post_act, has_res, out_code=None, logits=False, pad4=None) -> ConvDesc:
         """`pad4`: per-call (left, right, top, bottom) padding overriding the block's own (never stored on the runner)."""
@@ -360,15 +452,7 @@ class ConvRunner(object):
         key = self._state_key(x.dtype, x.cpitch, d)
         if key == self._key:
             return
-        if self._foreign:
-            # the packed state came from another rank; a new key (another dtype / channel pitch / padding parity / output type, or
-            # touched parameters) would re-pack from THIS rank's fp32 tensors, which broadcast_packed_state never updated: wrong
-            # logits with no error. Refuse; the caller re-synchronises the fp32 state first.
-            raise RuntimeError(
-                "this convolution's packed weights were received by parallel.broadcast_packed_state and would have to be re-packed "
-                "(the input's dtype / channel pitch / padding parity or a parameter changed), but this rank's fp32 parameters are "
-                "not the source's. Call parallel.broadcast_module_state(net) (or load_state_dict on every rank) before running "
-                "another configuration.")
+        self._rebuilding()
         dev = x.device
         w = self.conv.weight
         if w.device != dev:
@@ -383,43 +467,19 @@ class ConvRunner(object):
         w32 = w.detach().float()
         if w32.dim() == 2:                                          # nn.Linear viewed as a 1x1 convolution
             w32 = w32[:, :, None, None]
-        C, Cl = d.Cout, self.conv.out_channels                      # physical / logical output channels
+        C = d.Cout                                                  # physical output channels
         cin_g = d.Cin // d.groups                                   # physical input channels per group
         if w32.shape[0] != C or w32.shape[1] != cin_g:              # zero rows / columns for the pad channels
             w32 = F.pad(w32, (0, 0, 0, 0, 0, cin_g - w32.shape[1], 0, C - w32.shape[0]))
         w32 = w32.contiguous()
         _call(dev, "dwconv_pack" if self.depthwise else "conv_pack", ctypes.byref(d), _ptr(w32), _ptr(packed))
-
-        def padded(t, fill):
-            t = t.detach().float()
-            return (F.pad(t, (0, C - Cl), value=fill) if C != Cl else t).contiguous()
-        scale = torch.empty(C, dtype=torch.float32, device=dev)
-        shift = torch.empty(C, dtype=torch.float32, device=dev)
-        bias = padded(self.conv.bias, 0.0) if self.conv.bias is not None else None
-        if self.bn is not None:
-            if not isinstance(self.bn, nn.BatchNorm2d):
-                raise NotImplementedError("only BatchNorm2d folds into the conv epilogue, got {}".format(type(self.bn).__name__))
-            # pad channels: gamma 0, beta 0 -> scale 0, shift 0
-            g = padded(self.bn.weight, 0.0) if self.bn.weight is not None else padded(torch.ones(Cl, device=dev), 0.0)
-            b = padded(self.bn.bias, 0.0) if self.bn.bias is not None else torch.zeros(C, device=dev)
-            m = padded(self.bn.running_mean, 0.0)
-            v = padded(self.bn.running_var, 1.0)
-            _call(dev, "bn_fold", C, _ptr(g), _ptr(b), _ptr(m), _ptr(v), ctypes.c_float(self.bn.eps), _ptr(bias), _ptr(scale), _ptr(shift))
-        else:
-            _call(dev, "bn_fold", C, None, None, None, None, ctypes.c_float(0.0), _ptr(bias), _ptr(scale), _ptr(shift))
+        scale, shift = _fold_bn(dev, self.bn, C, self.conv.bias)
         torch.cuda.current_stream(dev).synchronize()      # w32 & friends are temporaries; load-time only
         self.packed, self.scale, self.shift, self._key = packed, scale, shift, key
 
     def adopt_foreign_state(self):
-        """Called after packed / scale / shift were overwritten with another rank's (parallel.broadcast_packed_state): the
-        cache key stays valid for exactly the configuration it was built for, anything else raises in prepare()."""
-        self._foreign = True
+        super(ConvRunner, self).adopt_foreign_state()
         self._sq_key = None
-
-    def local_state_restored(self):
-        """The fp32 sources are authoritative again (parallel.broadcast_module_state, load_state_dict): re-pack on next use."""
-        self._foreign = False
-        self._key = None
 
     def run(self, x: NHWC, act=0, residual: NHWC | None = None, post_act=0, out_fp32=False, pad4=None, out=None, gate=None) -> NHWC:
         """`pad4`: explicit (left, right, top, bottom) zero padding for this call (the `F.pad` a unit applies in front of
@@ -449,8 +509,7 @@ class ConvRunner(object):
         if Ho <= 0 or Wo <= 0:
             return None
         y = torch.empty((x.N, Ho, Wo, d.Cout), dtype=x.dtype, device=x.device)
-        _call(x.device, "conv2d_nchw_stem_fused", ctypes.byref(d), _ptr(x.src), _ptr(self.packed), _ptr(self.scale), _ptr(self.shift),
-              _ptr(y), 1 if pool else 0)
+        _call(x.device, "conv2d_nchw_stem_fused", ctypes.byref(d), _ptr(x.src), *_ptrs(self), _ptr(y), 1 if pool else 0)
         return NHWC(y, x.N, Ho, Wo, self.conv.out_channels, cpitch=d.Cout)
 
     def run_maxpool(self, x: NHWC, act: int, k: int, s: int, p: int, ceil_mode: bool = False):
@@ -472,8 +531,7 @@ class ConvRunner(object):
         if Hq <= 0 or Wq <= 0:
             return None
         y = torch.empty((x.N, Hq, Wq, d.Cout), dtype=x.dtype, device=x.device)
-        _call(x.device, "conv2d_maxpool_fused", ctypes.byref(d), _ptr(x.t), _ptr(self.packed), _ptr(self.scale), _ptr(self.shift),
-              _ptr(y), k, s, p, 1 if ceil_mode else 0)
+        _call(x.device, "conv2d_maxpool_fused", ctypes.byref(d), _ptr(x.t), *_ptrs(self), _ptr(y), k, s, p, 1 if ceil_mode else 0)
         return NHWC(y, x.N, Hq, Wq, self.conv.out_channels, cpitch=d.Cout)
 
     def run_pair(self, x: NHWC, residual: NHWC, act: int, post_act: int, nxt: "ConvRunner", nxt_act: int, gate=None):
@@ -485,12 +543,11 @@ class ConvRunner(object):
         c = self.conv
         L = _lib.lib()
         d1 = self.desc(x, act, post_act, True)
-        d2 = nxt.desc(_ShapeOnly(x.N, x.H, x.W, c.out_channels, x.dtype), nxt_act, 0, False)
+        d2 = nxt.desc(ShapeOnly(x.N, x.H, x.W, c.out_channels, x.dtype), nxt_act, 0, False)
         supported = L.pcv_conv1x1_pair_gated_supported if gate is not None else L.pcv_conv1x1_pair_supported
         if not supported(ctypes.byref(d1), ctypes.byref(d2)):
             return None
-        if not residual.dense or residual.dtype != x.dtype or tuple(residual.t.shape) != (x.N, x.H, x.W, d1.Cout):
-            raise RuntimeError("residual shape/dtype mismatch")
+        _check_residual(residual, (x.N, x.H, x.W, d1.Cout), x.dtype)
         if gate is not None and (gate.dtype != torch.float32 or tuple(gate.shape) != (x.N, d1.Cout) or not gate.is_contiguous()):
             raise RuntimeError("gate must be a contiguous fp32 [N, {}] tensor".format(d1.Cout))
         t1 = torch.empty((x.N, x.H, x.W, d1.Cout), dtype=x.dtype, device=x.device)
@@ -498,8 +555,8 @@ class ConvRunner(object):
         y1 = NHWC(t1, x.N, x.H, x.W, c.out_channels, cpitch=d1.Cout)
         self.prepare(x, d1)
         nxt.prepare(y1, d2)
-        first = (ctypes.byref(d1), ctypes.byref(d2), _ptr(x.t), _ptr(self.packed), _ptr(self.scale), _ptr(self.shift))
-        second = (_ptr(residual.t), _ptr(t1), _ptr(nxt.packed), _ptr(nxt.scale), _ptr(nxt.shift), _ptr(t2))
+        first = (ctypes.byref(d1), ctypes.byref(d2), _ptr(x.t), *_ptrs(self))
+        second = (_ptr(residual.t), _ptr(t1), *_ptrs(nxt), _ptr(t2))
         if gate is not None:
             _call(x.device, "conv1x1_pair_gated_fused", *first, _ptr(gate), *second)
         else:
@@ -518,7 +575,7 @@ class ConvRunner(object):
         c = self.conv
         di = idr.desc(x0, 0, 0, False)
         d1 = self.desc(x, act, post_act, True)
-        d2 = nxt.desc(_ShapeOnly(x.N, x.H, x.W, c.out_channels, x.dtype), nxt_act, 0, False)
+        d2 = nxt.desc(ShapeOnly(x.N, x.H, x.W, c.out_channels, x.dtype), nxt_act, 0, False)
         if not _lib.lib().pcv_conv1x1_pair_idconv_supported(ctypes.byref(di), ctypes.byref(d1), ctypes.byref(d2)):
             return None
         t1 = torch.empty((x.N, x.H, x.W, d1.Cout), dtype=x.dtype, device=x.device)
@@ -527,9 +584,8 @@ class ConvRunner(object):
         idr.prepare(x0, di)
         self.prepare(x, d1)
         nxt.prepare(y1, d2)
-        _call(x.device, "conv1x1_pair_idconv_fused", ctypes.byref(di), ctypes.byref(d1), ctypes.byref(d2), _ptr(x0.t), _ptr(idr.packed),
-              _ptr(idr.scale), _ptr(idr.shift), _ptr(x.t), _ptr(self.packed), _ptr(self.scale), _ptr(self.shift), _ptr(t1),
-              _ptr(nxt.packed), _ptr(nxt.scale), _ptr(nxt.shift), _ptr(t2))
+        _call(x.device, "conv1x1_pair_idconv_fused", ctypes.byref(di), ctypes.byref(d1), ctypes.byref(d2), _ptr(x0.t), *_ptrs(idr),
+              _ptr(x.t), *_ptrs(self), _ptr(t1), *_ptrs(nxt), _ptr(t2))
         return y1, NHWC(t2, x.N, x.H, x.W, nxt.conv.out_channels, cpitch=d2.Cout)
 
     def _launch(self, x: NHWC, d: ConvDesc, residual, out=None, gate=None):
@@ -549,30 +605,20 @@ class ConvRunner(object):
             y = buf[:, :, :, coff:]                 # a view: its data_ptr is the first element of the slice
         else:
             y = torch.empty((x.N, Ho, Wo, d.Cout), dtype=out_dt, device=x.device)          # d.Cout: physical channels
-        if residual is not None:
-            if not residual.dense or tuple(residual.t.shape) != (x.N, Ho, Wo, d.Cout) or residual.dtype != x.dtype:
-                raise RuntimeError("residual shape/dtype mismatch: {} vs {}".format(
-                    tuple(residual.t.shape), (x.N, Ho, Wo, d.Cout)))
+        _check_residual(residual, (x.N, Ho, Wo, d.Cout), x.dtype, detail=True)
         if gate is not None:
             if self.depthwise or gate.dtype != torch.float32 or tuple(gate.shape) != (x.N, d.Cout) or not gate.is_contiguous():
                 raise RuntimeError("gate must be a contiguous fp32 [N, {}] tensor of a dense convolution".format(d.Cout))
-        self._launch_range(x, d, residual, y, 0, x.N, gate)
-        return None if out is not None else NHWC(y, x.N, Ho, Wo, c.out_channels, cpitch=d.Cout)
 
-    def _launch_range(self, x, d, residual, y, n0, n1, gate=None):
-        """Launch images [n0, n1); halve the range when one launch would exceed the 2 GiB addressing window."""
-        d.N = n1 - n0
-        args = (ctypes.byref(d), _ptr(x.t[n0:n1]), _ptr(self.packed), _ptr(self.scale), _ptr(self.shift))
-        rest = (_ptr(residual.t[n0:n1]) if residual is not None else None, _ptr(y[n0:n1]))
-        halve = (_lib.PCV_ERR_TOO_LARGE,) if n1 - n0 > 1 else ()
-        if gate is not None:
-            rc = _call(x.device, "conv2d_gated_fused", *args, _ptr(gate[n0:n1]), *rest, accept=halve)
-        else:
-            rc = _call(x.device, "dwconv2d_fused" if self.depthwise else "conv2d_fused", *args, *rest, accept=halve)
-        if rc != 0:
-            mid = (n0 + n1) // 2
-            self._launch_range(x, d, residual, y, n0, mid, gate)
-            self._launch_range(x, d, residual, y, mid, n1, gate)
+        def launch(n0, n1, accept):
+            d.N = n1 - n0
+            args = (ctypes.byref(d), _ptr(x.t[n0:n1]), *_ptrs(self))
+            rest = (_ptr(residual.t[n0:n1]) if residual is not None else None, _ptr(y[n0:n1]))
+            if gate is not None:
+                return _call(x.device, "conv2d_gated_fused", *args, _ptr(gate[n0:n1]), *rest, accept=accept)
+            return _call(x.device, "dwconv2d_fused" if self.depthwise else "conv2d_fused", *args, *rest, accept=accept)
+        _split_batch(x.N, launch)
+        return None if out is not None else NHWC(y, x.N, Ho, Wo, c.out_channels, cpitch=d.Cout)
 
     def squeezed_excite(self, z: NHWC, w1, b1, w2, b2, mid_act: int, out_act: int) -> torch.Tensor:
         """SE gate of `SEBlock(BN(conv(z)))` for a 1x1 stride-1 convolution WITHOUT activation, computed before the convolution
@@ -585,8 +631,8 @@ class ConvRunner(object):
             raise RuntimeError("squeezed_excite needs a plain 1x1 stride-1 convolution")
         d = self.desc(z, 0, 0, False)
         self.prepare(z, d)                                   # scale / shift of the folded BatchNorm (+ bias)
-        key = ("sq", self._key) + tuple((t.data_ptr(), t._version) for t in (w1, w2, b1, b2))
-        if getattr(self, "_sq_key", None) != key:
+        key = ("sq", self._key) + source_key((w1, w2, b1, b2))
+        if self._sq_key != key:
             Cl, CP = c.out_channels, d.Cout
             w = c.weight.detach().float().reshape(Cl, -1)
             w = F.pad(w, (0, d.Cin - w.shape[1], 0, CP - Cl)) * self.scale[:, None]       # [CP, Cin]: BN scale folded into the rows
@@ -613,21 +659,21 @@ class MixConvRunner(ConvRunner):
     BatchNorm over all channels. One launch per block (pcv_mixconv2d_fused): every group reads and writes its channel slice in place.
     A ConvRunner as far as the packed-state plumbing goes (cache key, parallel.broadcast_packed_state).
     """
+    _refusal = ("this MixConv's packed weights were received by parallel.broadcast_packed_state and would have to be "
+                "re-packed: call parallel.broadcast_module_state(net) first")
+
     def __init__(self, convs, bn):
         self.convs = list(convs)
-        self.conv, self.bn, self.pad4 = self.convs[0], bn, None
-        self._key = None
-        self._foreign = False
-        self.packed = self.scale = self.shift = None
-        self.depthwise = True
         G = len(self.convs)
         for g, c in enumerate(self.convs):
             k = 3 + 2 * g
             if _pair(c.kernel_size) != (k, k) or _pair(c.padding) != (k // 2, k // 2) or _pair(c.dilation) != (1, 1) or \
-                    c.groups != c.in_channels or c.in_channels != c.out_channels or _pair(c.stride) != _pair(self.conv.stride) or \
+                    c.groups != c.in_channels or c.in_channels != c.out_channels or _pair(c.stride) != _pair(self.convs[0].stride) or \
                     c.padding_mode != "zeros":
                 raise NotImplementedError("MixConv on the MI355X path: depthwise groups with windows 3, 5, ... and padding k // 2, "
                                           "got group {} = {}".format(g, c))
+        super(MixConvRunner, self).__init__(self.convs[0], bn)      # `conv`: group 0, whose stride is every group's
+        self.depthwise = True                                       # (also where group 0 is a single channel: groups == 1)
         if not 2 <= G <= 5:
             raise NotImplementedError("MixConv with {} kernels: the MI355X path takes 2 to 5".format(G))
         self.channels = sum(c.out_channels for c in self.convs)
@@ -641,6 +687,9 @@ class MixConvRunner(ConvRunner):
             ts += [self.bn.weight, self.bn.bias, self.bn.running_mean, self.bn.running_var]
         return ts
 
+    def _state_key(self, dtype, cpitch, d: ConvDesc):
+        return (dtype, d.Cin) + source_key(self._sources())
+
     def desc(self, x: NHWC, act: int) -> ConvDesc:
         C, G = self.channels, len(self.convs)
         if not x.dense or x.C != C or x.cpitch != C:
@@ -653,12 +702,10 @@ class MixConvRunner(ConvRunner):
                         out_dtype=code, x_cpitch=C, x_wpitch=x.W)
 
     def prepare(self, x: NHWC, d: ConvDesc):
-        key = (x.dtype, d.Cin) + tuple((t.data_ptr(), t._version) if t is not None else None for t in self._sources())
+        key = self._state_key(x.dtype, x.cpitch, d)
         if key == self._key:
             return
-        if self._foreign:
-            raise RuntimeError("this MixConv's packed weights were received by parallel.broadcast_packed_state and would have to be "
-                               "re-packed: call parallel.broadcast_module_state(net) first")
+        self._rebuilding()
         dev, C, G = x.device, d.Cin, len(self.convs)
         if self.conv.weight.device != dev:
             raise RuntimeError("model parameters are on {} but the input is on {}".format(self.conv.weight.device, dev))
@@ -669,22 +716,11 @@ class MixConvRunner(ConvRunner):
         packed = torch.empty((nbytes.value + 15) // 16 * 16, dtype=torch.uint8, device=dev)
         ws = [c.weight.detach().float().contiguous() for c in self.convs]
         _call(dev, "mixconv_pack", ctypes.byref(d), self.kernels, G, (ctypes.c_void_p * G)(*[w.data_ptr() for w in ws]), _ptr(packed))
-        scale = torch.empty(C, dtype=torch.float32, device=dev)
-        shift = torch.empty(C, dtype=torch.float32, device=dev)
         bias = None
         if any(c.bias is not None for c in self.convs):
             bias = torch.cat([c.bias.detach().float() if c.bias is not None else torch.zeros(c.out_channels, device=dev)
-                              for c in self.convs]).contiguous()
-        bn = self.bn
-        if bn is not None:
-            if not isinstance(bn, nn.BatchNorm2d):
-                raise NotImplementedError("only BatchNorm2d folds into the conv epilogue, got {}".format(type(bn).__name__))
-            g = (bn.weight if bn.weight is not None else torch.ones(C, device=dev)).detach().float().contiguous()
-            b = (bn.bias if bn.bias is not None else torch.zeros(C, device=dev)).detach().float().contiguous()
-            m, v = bn.running_mean.detach().float().contiguous(), bn.running_var.detach().float().contiguous()
-            _call(dev, "bn_fold", C, _ptr(g), _ptr(b), _ptr(m), _ptr(v), ctypes.c_float(bn.eps), _ptr(bias), _ptr(scale), _ptr(shift))
-        else:
-            _call(dev, "bn_fold", C, None, None, None, None, ctypes.c_float(0.0), _ptr(bias), _ptr(scale), _ptr(shift))
+                              for c in self.convs])
+        scale, shift = _fold_bn(dev, self.bn, C, bias)
         torch.cuda.current_stream(dev).synchronize()      # the fp32 copies are temporaries; load-time only
         self.packed, self.scale, self.shift, self._key = packed, scale, shift, key
 
@@ -694,18 +730,13 @@ class MixConvRunner(ConvRunner):
         self.prepare(x, d)
         Ho, Wo = _conv_out(d, x.H, x.W)
         y = torch.empty((x.N, Ho, Wo, d.Cout), dtype=x.dtype, device=x.device)
-        self._launch_range(x, d, None, y, 0, x.N)
-        return NHWC(y, x.N, Ho, Wo, self.channels, cpitch=d.Cout)
 
-    def _launch_range(self, x, d, residual, y, n0, n1, gate=None):
-        """Launch images [n0, n1); halve the range when one launch would exceed the 2 GiB addressing window."""
-        d.N = n1 - n0
-        rc = _call(x.device, "mixconv2d_fused", ctypes.byref(d), self.kernels, len(self.convs), _ptr(x.t[n0:n1]), _ptr(self.packed),
-                   _ptr(self.scale), _ptr(self.shift), _ptr(y[n0:n1]), accept=(_lib.PCV_ERR_TOO_LARGE,) if n1 - n0 > 1 else ())
-        if rc != 0:
-            mid = (n0 + n1) // 2
-            self._launch_range(x, d, None, y, n0, mid)
-            self._launch_range(x, d, None, y, mid, n1)
+        def launch(n0, n1, accept):
+            d.N = n1 - n0
+            return _call(x.device, "mixconv2d_fused", ctypes.byref(d), self.kernels, len(self.convs), _ptr(x.t[n0:n1]), *_ptrs(self),
+                         _ptr(y[n0:n1]), accept=accept)
+        _split_batch(x.N, launch)
+        return NHWC(y, x.N, Ho, Wo, self.channels, cpitch=d.Cout)
 
 
 def ghost_dw(runner: ConvRunner, m: NHWC, act: int, residual: NHWC | None = None) -> NHWC:
@@ -731,21 +762,14 @@ def ghost_dw(runner: ConvRunner, m: NHWC, act: int, residual: NHWC | None = None
         raise NotImplementedError("ghost module ({} + {} channels on a {}x{} map) is not covered by the MI355X path: {}".format(
             Cm, Cm, m.H, m.W, (L.pcv_last_error(None) or b"").decode()))
     runner.prepare(m, dp)
-    if residual is not None:
-        if not residual.dense or tuple(residual.t.shape) != (m.N, m.H, m.W, 2 * Cm) or residual.dtype != m.dtype:
-            raise RuntimeError("residual shape/dtype mismatch: {} vs {}".format(tuple(residual.t.shape), (m.N, m.H, m.W, 2 * Cm)))
+    _check_residual(residual, (m.N, m.H, m.W, 2 * Cm), m.dtype, detail=True)
     y = torch.empty((m.N, m.H, m.W, 2 * Cm), dtype=m.dtype, device=m.device)
 
-    def launch(n0, n1):                                 # images [n0, n1); halved when one launch would exceed the 2 GiB window
+    def launch(n0, n1, accept):
         d.N = n1 - n0
-        rc = _call(m.device, "ghost_dw_fused", ctypes.byref(d), _ptr(m.t[n0:n1]), _ptr(runner.packed), _ptr(runner.scale),
-                   _ptr(runner.shift), _ptr(residual.t[n0:n1]) if residual is not None else None, _ptr(y[n0:n1]),
-                   accept=(_lib.PCV_ERR_TOO_LARGE,) if n1 - n0 > 1 else ())
-        if rc != 0:
-            mid = (n0 + n1) // 2
-            launch(n0, mid)
-            launch(mid, n1)
-    launch(0, m.N)
+        return _call(m.device, "ghost_dw_fused", ctypes.byref(d), _ptr(m.t[n0:n1]), *_ptrs(runner),
+                     _ptr(residual.t[n0:n1]) if residual is not None else None, _ptr(y[n0:n1]), accept=accept)
+    _split_batch(m.N, launch)
     return NHWC(y, m.N, m.H, m.W, 2 * Cm, cpitch=2 * Cm)
 
 
@@ -908,28 +932,23 @@ def mbconv_fused(exp, exp_act: int, dw, dw_act: int, proj, proj_act: int, x: NHW
     d_exp = None
     if exp is not None:
         d_exp = exp.desc(x, exp_act, 0, False)
-        cur = _ShapeOnly(x.N, x.H, x.W, exp.conv.out_channels, x.dtype)
+        cur = ShapeOnly(x.N, x.H, x.W, exp.conv.out_channels, x.dtype, x.device)
     d_dw = dw.desc(cur, dw_act, 0, False)
     Ho, Wo = _conv_out(d_dw, cur.H, cur.W)
-    mid = _ShapeOnly(x.N, Ho, Wo, dw.conv.out_channels, x.dtype)
+    mid = ShapeOnly(x.N, Ho, Wo, dw.conv.out_channels, x.dtype, x.device)
     d_proj = proj.desc(mid, proj_act, post_act, residual is not None)
     if not _lib.lib().pcv_mbconv_supported(ctypes.byref(d_exp) if d_exp is not None else None, ctypes.byref(d_dw), ctypes.byref(d_proj)):
         return None
     Cout = d_proj.Cout                                           # physical
-    if residual is not None and (not residual.dense or residual.dtype != x.dtype or
-                                 tuple(residual.t.shape) != (x.N, Ho, Wo, Cout)):
-        raise RuntimeError("residual shape/dtype mismatch")
+    _check_residual(residual, (x.N, Ho, Wo, Cout), x.dtype)
     # weights / BN constants are packed through the runners' own caches (dense handles of the right shape and dtype)
     if exp is not None:
         exp.prepare(x, d_exp)
-    dw.prepare(_PrepHandle(cur, x.device), d_dw)
-    proj.prepare(_PrepHandle(mid, x.device), d_proj)
+    dw.prepare(cur, d_dw)
+    proj.prepare(mid, d_proj)
     y = torch.empty((x.N, Ho, Wo, Cout), dtype=x.dtype, device=x.device)
     _call(x.device, "mbconv_fused", ctypes.byref(d_exp) if d_exp is not None else None, ctypes.byref(d_dw), ctypes.byref(d_proj),
-          _ptr(x.t), _ptr(exp.packed) if exp is not None else None,
-          _ptr(exp.scale) if exp is not None else None, _ptr(exp.shift) if exp is not None else None,
-          _ptr(dw.packed), _ptr(dw.scale), _ptr(dw.shift), _ptr(proj.packed), _ptr(proj.scale),
-          _ptr(proj.shift), _ptr(residual.t) if residual is not None else None, _ptr(y))
+          _ptr(x.t), *_ptrs(exp), *_ptrs(dw), *_ptrs(proj), _ptr(residual.t) if residual is not None else None, _ptr(y))
     return NHWC(y, x.N, Ho, Wo, proj.conv.out_channels, cpitch=Cout)
 
 
@@ -937,25 +956,25 @@ def bottleneck_fused(c1, act1: int, c2, act2: int, c3, act3: int, x: NHWC, post_
     """A whole bottleneck unit - 1x1 -> 3x3 -> 1x1, + skip, + post_act - as ONE launch (pcv_bottleneck_fused): `c1`, `c2`, `c3` are
     the ConvRunners of the body's blocks; the skip is `x` itself or, with `idr` (the runner of the unit's `identity_conv`), that
     convolution of `x`, computed inside the launch. Returns the unit output, or None when the unit is not covered (the caller then
-    issues the separate launches). `probe`: `x` is a _ShapeOnly; returns whether a dense input of that shape would be covered."""
+    issues the separate launches). `probe`: `x` is a ShapeOnly; returns whether a dense input of that shape would be covered."""
     runners = (c1, c2, c3) + ((idr,) if idr is not None else ())
-    if not FUSE_UNITS or not (probe or x.dense) or any(r.depthwise or r.pad4 is not None for r in runners):
+    if not FUSE_UNITS or not x.dense or any(r.depthwise or r.pad4 is not None for r in runners):
         return None
     _require_eval(*runners)
     # every bottleneck unit of every stage asks on every forward, and an eager forward at batch 1 is bound by this host code: what the
     # library refused once for a shape is not asked again (three descriptors and a call per unit; a refusal only ever means the
     # separate launches, so a remembered one is safe even if pcv_set_tuning("bnu", ...) changes later)
     key = (x.N, x.H, x.W, x.dtype, x.cpitch, act1, act2, act3, post_act, idr is not None)
-    refused = c1.__dict__.setdefault("_bnu_refused", set())
+    refused = c1._bnu_refused
     if key in refused:
         return None
     d1 = c1.desc(x, act1, 0, False)
-    t1 = _ShapeOnly(x.N, x.H, x.W, c1.conv.out_channels, x.dtype)
+    t1 = ShapeOnly(x.N, x.H, x.W, c1.conv.out_channels, x.dtype, x.device)
     d2 = c2.desc(t1, act2, 0, False)
     if _conv_out(d2, x.H, x.W) != (x.H, x.W):
         refused.add(key)
         return None
-    t2 = _ShapeOnly(x.N, x.H, x.W, c2.conv.out_channels, x.dtype)
+    t2 = ShapeOnly(x.N, x.H, x.W, c2.conv.out_channels, x.dtype, x.device)
     d3 = c3.desc(t2, act3, post_act, True)
     di = idr.desc(x, 0, 0, False) if idr is not None else None
     if not _lib.lib().pcv_bottleneck_supported(ctypes.byref(d1), ctypes.byref(d2), ctypes.byref(d3),
@@ -965,73 +984,45 @@ def bottleneck_fused(c1, act1: int, c2, act2: int, c3, act3: int, x: NHWC, post_
     if probe:
         return True
     c1.prepare(x, d1)
-    c2.prepare(_PrepHandle(t1, x.device), d2)
-    c3.prepare(_PrepHandle(t2, x.device), d3)
+    c2.prepare(t1, d2)
+    c3.prepare(t2, d3)
     if idr is not None:
         idr.prepare(x, di)
     y = torch.empty((x.N, x.H, x.W, d3.Cout), dtype=x.dtype, device=x.device)
     _call(x.device, "bottleneck_fused", ctypes.byref(d1), ctypes.byref(d2), ctypes.byref(d3), ctypes.byref(di) if di is not None else None,
-          _ptr(x.t), _ptr(c1.packed), _ptr(c1.scale), _ptr(c1.shift), _ptr(c2.packed), _ptr(c2.scale), _ptr(c2.shift),
-          _ptr(c3.packed), _ptr(c3.scale), _ptr(c3.shift), _ptr(idr.packed) if idr is not None else None,
-          _ptr(idr.scale) if idr is not None else None, _ptr(idr.shift) if idr is not None else None, _ptr(y))
+          _ptr(x.t), *_ptrs(c1), *_ptrs(c2), *_ptrs(c3), *_ptrs(idr), _ptr(y))
     return NHWC(y, x.N, x.H, x.W, c3.conv.out_channels, cpitch=d3.Cout)
 
 
-class _PrepHandle(object):
-    """dtype / cpitch / device of a tensor that is never materialised, for ConvRunner.prepare."""
-    __slots__ = ("dtype", "cpitch", "device")
-
-    def __init__(self, shape_only, device):
-        self.dtype, self.cpitch, self.device = shape_only.dtype, shape_only.cpitch, device
-
-
-class BnActRunner(object):
+class BnActRunner(_DerivedState):
     """Eval-mode BatchNorm2d + activation as one elementwise launch (pcv_bn_act); scale/shift are folded once and refolded
-    when the parameters change (same cache rule as ConvRunner)."""
+    when the parameters change (same cache rule as ConvRunner; `packed` stays None)."""
+    _refusal = ("this BatchNorm's folded constants were received by parallel.broadcast_packed_state and its local "
+                "parameters changed: call parallel.broadcast_module_state(net) first")
+
+    _sq_key = None      # (no SE squeeze map folds through a BatchNorm: see ConvRunner.squeezed_excite; parallel asks every runner)
+
     def __init__(self, bn):
+        super(BnActRunner, self).__init__()
         self.bn = bn
-        self._key = None
-        self._foreign = False       # see ConvRunner._foreign
-        self.scale = self.shift = None
+
+    def _sources(self):
+        return [self.bn.weight, self.bn.bias, self.bn.running_mean, self.bn.running_var]
 
     def _state_key(self):
-        ts = (self.bn.weight, self.bn.bias, self.bn.running_mean, self.bn.running_var)
-        return tuple((t.data_ptr(), t._version) if t is not None else None for t in ts)
+        return source_key(self._sources())
 
     def prepare(self, x: NHWC):
         key = self._state_key()
         if key == self._key:
             return
-        if self._foreign:
-            raise RuntimeError("this BatchNorm's folded constants were received by parallel.broadcast_packed_state and its local "
-                               "parameters changed: call parallel.broadcast_module_state(net) first")
+        self._rebuilding()
         bn, dev = self.bn, x.device
-        if not isinstance(bn, nn.BatchNorm2d):
-            raise NotImplementedError("only BatchNorm2d folds to scale/shift, got {}".format(type(bn).__name__))
-        if bn.running_mean.device != dev:
+        if isinstance(bn, nn.BatchNorm2d) and bn.running_mean.device != dev:
             raise RuntimeError("model parameters are on {} but the input is on {}".format(bn.running_mean.device, dev))
-        Cl = bn.num_features
-        C = round8(Cl)                                          # pad channels: scale 0, shift 0
-
-        def padded(t, fill):
-            t = t.detach().float()
-            return (F.pad(t, (0, C - Cl), value=fill) if C != Cl else t).contiguous()
-        g = padded(bn.weight if bn.weight is not None else torch.ones(Cl, device=dev), 0.0)
-        b = padded(bn.bias if bn.bias is not None else torch.zeros(Cl, device=dev), 0.0)
-        m = padded(bn.running_mean, 0.0)
-        v = padded(bn.running_var, 1.0)
-        scale = torch.empty(C, dtype=torch.float32, device=dev)
-        shift = torch.empty(C, dtype=torch.float32, device=dev)
-        _call(dev, "bn_fold", C, _ptr(g), _ptr(b), _ptr(m), _ptr(v), ctypes.c_float(bn.eps), None, _ptr(scale), _ptr(shift))
+        scale, shift = _fold_bn(dev, bn, round8(bn.num_features), what="to scale/shift")
         torch.cuda.current_stream(dev).synchronize()
         self.scale, self.shift, self._key = scale, shift, key
-
-    def adopt_foreign_state(self):
-        self._foreign = True
-
-    def local_state_restored(self):
-        self._foreign = False
-        self._key = None
 
     def run(self, x: NHWC, act: int) -> NHWC:
         _require_eval(self)
@@ -1068,11 +1059,7 @@ class IBNConvRunner(ConvRunner):
         h1, h2 = self.ibn.split_sections
         if d.Cout != h1 + h2 or bn.num_features != h2:
             raise RuntimeError("IBN sections {} do not cover the convolution's {} output channels".format((h1, h2), d.Cout))
-        g, b, m, v = [t.detach().float().contiguous() for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)]
-        bias = self.conv.bias[h1:].detach().float().contiguous() if self.conv.bias is not None else None
-        scale = torch.empty(h2, dtype=torch.float32, device=dev)
-        shift = torch.empty(h2, dtype=torch.float32, device=dev)
-        _call(dev, "bn_fold", h2, _ptr(g), _ptr(b), _ptr(m), _ptr(v), ctypes.c_float(bn.eps), _ptr(bias), _ptr(scale), _ptr(shift))
+        scale, shift = _fold_bn(dev, bn, h2, self.conv.bias[h1:] if self.conv.bias is not None else None)
         self.scale[h1:].copy_(scale)
         self.shift[h1:].copy_(shift)
         torch.cuda.current_stream(dev).synchronize()

@@ -62,17 +62,12 @@ class SEBlock(nn.Module):
                 not conv_block.use_pad and c is not None and tuple(c.kernel_size) == (1, 1) and tuple(c.stride) == (1, 1) and
                 tuple(c.padding) == (0, 0) and c.groups == 1 and z.dense):
             return None
-        if conv_block._pcv_runner is None:
-            conv_block._pcv_runner = engine.ConvRunner(conv_block.conv, conv_block.bn if conv_block.normalize else None)
-        runner = conv_block._pcv_runner
+        runner = conv_block.runner()
         w1, b1, w2, b2 = self._mlp()
         gate = runner.squeezed_excite(z, w1, b1, w2, b2, engine.act_code(self.activ), engine.act_code(self.sigmoid))
         if next_conv is not None and residual is not None and isinstance(next_conv, ConvBlock):
             # ... and the next unit's first 1x1 in the same launch: returns (y, next conv1 output)
-            if next_conv._pcv_runner is None:
-                next_conv._pcv_runner = engine.ConvRunner(next_conv.conv, next_conv.bn if next_conv.normalize else None, pad4=next_conv._pad4)
-            pair = runner.run_pair(z, residual, 0, engine.act_code(post_act), next_conv._pcv_runner,
-                                   engine.act_code(next_conv.activ) if next_conv.activate else 0, gate=gate)
+            pair = runner.run_pair(z, residual, 0, engine.act_code(post_act), next_conv.runner(), next_conv.act_code(), gate=gate)
             if pair is not None:
                 return pair
         return runner.run(z, act=0, residual=residual, post_act=engine.act_code(post_act), gate=gate)
@@ -104,7 +99,7 @@ class _FoldedMlp(object):
         self.key, self.value = None, None
 
     def get(self, sources, build):
-        key = tuple((t.data_ptr(), t._version) if t is not None else None for t in sources)
+        key = engine.source_key(sources)
         if key != self.key:
             self.value, self.key = build(), key
         return self.value

@@ -69,25 +69,27 @@ class ConvBlock(nn.Module):
                 assert isinstance(self.activ, nn.Module)
         self._pcv_runner = None
 
+    def runner(self):
+        """This block's engine.ConvRunner, built on first use (parallel finds it as `_pcv_runner`)."""
+        if self._pcv_runner is None:
+            self._pcv_runner = engine.ConvRunner(self.conv, self.bn if self.normalize else None, pad4=self._pad4)
+        return self._pcv_runner
+
+    def act_code(self):
+        return engine.act_code(self.activ) if self.activate else 0
+
     def forward(self, x, residual=None, post_act=None, pad4=None, out=None):
         """`out` = (NHWC buffer [N, Ho, Wo, Ctot], channel offset): write the result into that channel slice (a concatenation
         without the copy: common/arch.py `Concurrent`); returns None then."""
-        if self._pcv_runner is None:
-            self._pcv_runner = engine.ConvRunner(self.conv, self.bn if self.normalize else None, pad4=self._pad4)
-        act = engine.act_code(self.activ) if self.activate else 0
-        pact = engine.act_code(post_act)
-        return engine.boundary(self, x, lambda a: self._pcv_runner.run(a, act=act, residual=residual, post_act=pact,
-                                                                       pad4=pad4, out=out))
+        runner, act, pact = self.runner(), self.act_code(), engine.act_code(post_act)
+        return engine.boundary(self, x, lambda a: runner.run(a, act=act, residual=residual, post_act=pact, pad4=pad4, out=out))
 
 
 def conv_block_maxpool(block, x, pool):
     """ConvBlock `block` followed by the MaxPool2dNHWC `pool` (an init block's `conv` -> `pool`): one fused launch when covered
     (pcv_conv2d_maxpool_fused), else the two launches."""
     if isinstance(block, ConvBlock) and isinstance(x, engine.NHWC) and not block.use_pad:
-        if block._pcv_runner is None:
-            block._pcv_runner = engine.ConvRunner(block.conv, block.bn if block.normalize else None, pad4=block._pad4)
-        y = block._pcv_runner.run_maxpool(x, engine.act_code(block.activ) if block.activate else 0, pool.kernel_size,
-                                          pool.stride, pool.padding, pool.ceil_mode)
+        y = block.runner().run_maxpool(x, block.act_code(), pool.kernel_size, pool.stride, pool.padding, pool.ceil_mode)
         if y is not None:
             return y
     return pool(block(x))
@@ -100,20 +102,12 @@ def conv_block_pair(first, x, residual, post_act, second, id_block=None, x0=None
     tensor is recomputed inside the launch (pcv_conv1x1_pair_idconv_fused)."""
     if not (isinstance(first, ConvBlock) and isinstance(second, ConvBlock) and isinstance(x, engine.NHWC)):
         return None
-    for blk in (first, second) + ((id_block,) if id_block is not None else ()):
-        if not isinstance(blk, ConvBlock):
-            return None
-        if blk._pcv_runner is None:
-            blk._pcv_runner = engine.ConvRunner(blk.conv, blk.bn if blk.normalize else None, pad4=blk._pad4)
     if id_block is not None:
-        if id_block.activate or not isinstance(x0, engine.NHWC):
+        if not isinstance(id_block, ConvBlock) or id_block.activate or not isinstance(x0, engine.NHWC):
             return None
-        return first._pcv_runner.run_pair_idconv(x, x0, id_block._pcv_runner, engine.act_code(first.activ) if first.activate else 0,
-                                                 engine.act_code(post_act), second._pcv_runner,
-                                                 engine.act_code(second.activ) if second.activate else 0)
-    return first._pcv_runner.run_pair(x, residual, engine.act_code(first.activ) if first.activate else 0,
-                                      engine.act_code(post_act), second._pcv_runner,
-                                      engine.act_code(second.activ) if second.activate else 0)
+        return first.runner().run_pair_idconv(x, x0, id_block.runner(), first.act_code(), engine.act_code(post_act),
+                                              second.runner(), second.act_code())
+    return first.runner().run_pair(x, residual, first.act_code(), engine.act_code(post_act), second.runner(), second.act_code())
 
 
 def mbconv_chain(exp_block, dw_block, proj_block, x, residual=None, post_act=None):
@@ -122,15 +116,9 @@ def mbconv_chain(exp_block, dw_block, proj_block, x, residual=None, post_act=Non
     blocks = [b for b in (exp_block, dw_block, proj_block) if b is not None]
     if not isinstance(x, engine.NHWC) or not all(isinstance(b, ConvBlock) for b in blocks):
         return None
-    for blk in blocks:
-        if blk._pcv_runner is None:
-            blk._pcv_runner = engine.ConvRunner(blk.conv, blk.bn if blk.normalize else None, pad4=blk._pad4)
-
-    def code(blk):
-        return engine.act_code(blk.activ) if blk.activate else 0
-    return engine.mbconv_fused(exp_block._pcv_runner if exp_block is not None else None,
-                               code(exp_block) if exp_block is not None else 0, dw_block._pcv_runner, code(dw_block),
-                               proj_block._pcv_runner, code(proj_block), x, residual, engine.act_code(post_act))
+    exp, exp_act = (exp_block.runner(), exp_block.act_code()) if exp_block is not None else (None, 0)
+    return engine.mbconv_fused(exp, exp_act, dw_block.runner(), dw_block.act_code(), proj_block.runner(), proj_block.act_code(),
+                               x, residual, engine.act_code(post_act))
 
 
 def conv_block_bottleneck(conv1, conv2, conv3, x, post_act, id_block=None, probe=False):
@@ -143,14 +131,8 @@ def conv_block_bottleneck(conv1, conv2, conv3, x, post_act, id_block=None, probe
         return None
     if id_block is not None and id_block.activate:
         return None
-    for blk in blocks:
-        if blk._pcv_runner is None:
-            blk._pcv_runner = engine.ConvRunner(blk.conv, blk.bn if blk.normalize else None, pad4=blk._pad4)
-
-    def code(blk):
-        return engine.act_code(blk.activ) if blk.activate else 0
-    return engine.bottleneck_fused(conv1._pcv_runner, code(conv1), conv2._pcv_runner, code(conv2), conv3._pcv_runner, code(conv3), x,
-                                   engine.act_code(post_act), id_block._pcv_runner if id_block is not None else None, probe=probe)
+    return engine.bottleneck_fused(conv1.runner(), conv1.act_code(), conv2.runner(), conv2.act_code(), conv3.runner(), conv3.act_code(),
+                                   x, engine.act_code(post_act), id_block.runner() if id_block is not None else None, probe=probe)
 
 
 def conv1x1_block(padding=0, **kwargs):

@@ -42,10 +42,7 @@ class GhostConvBlock(nn.Module):
 
     def _run(self, a, residual):
         cheap = self.cheap_conv
-        if cheap._pcv_runner is None:
-            cheap._pcv_runner = engine.ConvRunner(cheap.conv, cheap.bn if cheap.normalize else None)
-        m = self.main_conv(a)
-        return engine.ghost_dw(cheap._pcv_runner, m, engine.act_code(cheap.activ) if cheap.activate else 0, residual)
+        return engine.ghost_dw(cheap.runner(), self.main_conv(a), cheap.act_code(), residual)
 
     def forward(self, x, residual=None):
         return engine.boundary(self, x, lambda a: self._run(a, residual))

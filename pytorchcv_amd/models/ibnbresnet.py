@@ -33,7 +33,7 @@ class IBNbConvBlock(nn.Module):
         if self._pcv_runner is None:
             self._pcv_runner = engine.ConvRunner(self.conv, None)
             self._pcv_in = engine.InstNormRunner(self.inst_norm)
-        return self._pcv_in.run(self._pcv_runner.run(a, act=0), engine.act_code(self.activ) if self.activate else 0)
+        return self._pcv_in.run(self._pcv_runner.run(a, act=0), engine.act_code(self.activ if self.activate else None))
 
     def forward(self, x, stem=False):
         return engine.boundary(self, x, self._run, stem=stem)

@@ -41,7 +41,7 @@ class IBNConvBlock(nn.Module):
         self._pcv_runner = None
 
     def _run(self, a):
-        act = engine.act_code(self.activ) if self.activate else 0
+        act = engine.act_code(self.activ if self.activate else None)
         if self._pcv_runner is None:
             self._pcv_runner = engine.IBNConvRunner(self.conv, self.ibn) if self.use_ibn else engine.ConvRunner(self.conv, self.bn)
         if not self.use_ibn:

@@ -37,8 +37,7 @@ class _GroupedView(object):
         self._key = self._w = self._b = None
 
     def _refresh(self):
-        ts = [c.weight for c in self._convs] + [c.bias for c in self._convs]
-        key = tuple((t.data_ptr(), t._version) if t is not None else None for t in ts)
+        key = engine.source_key([c.weight for c in self._convs] + [c.bias for c in self._convs])
         if key != self._key:
             self._w = torch.cat([c.weight.detach() for c in self._convs], dim=0)
             self._b = torch.cat([c.bias.detach() for c in self._convs], dim=0) if self._convs[0].bias is not None else None

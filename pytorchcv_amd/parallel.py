@@ -99,7 +99,6 @@ def packed_state_tensors(module: torch.nn.Module):
         re-derives that map from the fp32 weights: its cache is dropped by the hook so that it is rebuilt from the received
         tensors).
     Every runner must already be built (one forward of the net on any input of the serving shape does that)."""
-    from . import engine
     tensors, hooks = [], []
     owned = set()
 
@@ -107,14 +106,13 @@ def packed_state_tensors(module: torch.nn.Module):
         for r in _runners_of(m):
             if r.scale is None or r.shift is None:
                 raise RuntimeError("packed state requested before the first forward built every runner")
-            if getattr(r, "packed", None) is not None:
+            if r.packed is not None:
                 tensors.append(r.packed)
             tensors += [r.scale, r.shift]
-            if getattr(r, "_sq_key", None) is not None:              # SE squeeze folded through this convolution: fp32 too
+            if r._sq_key is not None:                                # SE squeeze folded through this convolution: fp32 too
                 hooks.append(lambda r=r: setattr(r, "_sq_key", None))
                 continue
-            src = r._sources() if isinstance(r, engine.ConvRunner) else (r.bn.weight, r.bn.bias, r.bn.running_mean, r.bn.running_var)
-            owned.update(id(t) for t in src if t is not None)
+            owned.update(id(t) for t in r._sources() if t is not None)
     for _, t in sorted(module.state_dict(keep_vars=True).items()):
         if id(t) not in owned and t.dtype.is_floating_point:
             tensors.append(t.data)

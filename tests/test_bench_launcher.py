@@ -158,9 +158,8 @@ def test_runner_with_foreign_packed_state_refuses_to_repack():
     blk = Block().eval()
     r, b = blk._pcv_runner, blk._pcv_bnact
     cpu = torch.device("cpu")
-    s_bf = engine._ShapeOnly(1, 4, 4, 16, torch.bfloat16)
-    x = engine._PrepHandle(s_bf, cpu)                              # dtype / cpitch / device: all prepare() reads of its input
-    d = r.desc(s_bf, 0, 0, False)
+    x = engine.ShapeOnly(1, 4, 4, 16, torch.bfloat16, cpu)        # shape / dtype / cpitch / device: all desc() and prepare() read
+    d = r.desc(x, 0, 0, False)
     r._key = r._state_key(x.dtype, x.cpitch, d)                   # as if packed for this configuration
     r.packed, r.scale, r.shift = torch.zeros(1), torch.zeros(16), torch.zeros(16)
     b._key, b.scale, b.shift = b._state_key(), torch.zeros(16), torch.zeros(16)
@@ -168,12 +167,41 @@ def test_runner_with_foreign_packed_state_refuses_to_repack():
         q.adopt_foreign_state()                                   # what broadcast_packed_state does on ranks != src
     r.prepare(x, d)                                               # same key: the received state is used as is
     b.prepare(x)
-    s_16 = engine._ShapeOnly(1, 4, 4, 16, torch.float16)
+    x_16 = engine.ShapeOnly(1, 4, 4, 16, torch.float16, cpu)
     with pytest.raises(RuntimeError, match="broadcast_packed_state"):
-        r.prepare(engine._PrepHandle(s_16, cpu), r.desc(s_16, 0, 0, False))      # another dtype: would re-pack from the local fp32 weights
+        r.prepare(x_16, r.desc(x_16, 0, 0, False))                # another dtype: would re-pack from the local fp32 weights
     with torch.no_grad():
         blk.bn.weight.mul_(2.0)                                   # a touched parameter
     with pytest.raises(RuntimeError, match="broadcast_packed_state"):
         b.prepare(x)
     parallel.mark_local_state_authoritative(blk)                  # (or broadcast_module_state): local tensors are the truth again
     assert r._key is None and not r._foreign and not b._foreign
+
+    # the same sequence for the two other runners that are ConvRunners: a depthwise MixConv (two groups of 8 channels) and IBN
+    class MixBlock(nn.Module):
+        def __init__(self):
+            super(MixBlock, self).__init__()
+            self.convs = nn.ModuleList([nn.Conv2d(8, 8, 3 + 2 * g, padding=1 + g, groups=8, bias=False) for g in range(2)])
+            self.bn = nn.BatchNorm2d(16)
+            self._pcv_runner = engine.MixConvRunner(self.convs, self.bn)
+
+    class IBNBlock(nn.Module):
+        def __init__(self):
+            super(IBNBlock, self).__init__()
+            self.conv = nn.Conv2d(16, 16, 1, bias=False)
+            self.ibn = IBN(channels=16)
+            self._pcv_runner = engine.IBNConvRunner(self.conv, self.ibn)
+
+    from pytorchcv_amd.models.common.norm import IBN
+    for blk, desc in ((MixBlock().eval(), lambda q, h: q.desc(h, 0)), (IBNBlock().eval(), lambda q, h: q.desc(h, 0, 0, False))):
+        q, = parallel._runners(blk)
+        d = desc(q, x)
+        q._key = q._state_key(x.dtype, x.cpitch, d)
+        q.packed, q.scale, q.shift = torch.zeros(1), torch.zeros(16), torch.zeros(16)
+        q.adopt_foreign_state()
+        q.prepare(x, d)                                           # same key: accepted
+        assert q._foreign and q._key is not None
+        with pytest.raises(RuntimeError, match="broadcast_packed_state"):
+            q.prepare(x_16, desc(q, x_16))                        # another dtype
+        parallel.mark_local_state_authoritative(blk)
+        assert q._key is None and not q._foreign

@@ -172,7 +172,7 @@ def test_odd_num_classes_and_in_channels(cuda_device):
 
 def test_batch_split_beyond_2gib_window(cuda_device):
     """One launch addresses its input through a 32-bit buffer window (< 2 GiB); larger batches are split by the host
-    (PCV_ERR_TOO_LARGE -> ConvRunner._launch_range). The split result equals the per-chunk results bit for bit."""
+    (PCV_ERR_TOO_LARGE -> engine._split_batch). The split result equals the per-chunk results bit for bit."""
     import pytorchcv_amd
     from pytorchcv_amd import engine
     from pytorchcv_amd.models.common.conv import conv1x1_block, dwconv3x3_block
